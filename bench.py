@@ -17,10 +17,19 @@ The timed region starts with the tableau resident in HBM (upload excluded).  Ran
 `roofline`: the sweep / row-update launch is bounded below by one 16*m_local*n-byte pass at 8 TB/s and by its
 2*m_local*n*K unfusable fp64 operations at 39.3 T op/s; frac = the larger bound / the mean launch time measured with
 HIP events on the launch stream inside the timed region (<= 1), `bound` names the larger term (roofline_block).
-`parity_after_timed_region`: warm-up + steps pivots replayed on the fp64 oracle and compared bit for bit with what the
-timed handle holds.  `cpu_baseline` = the decimal-15 oracle (the reference's BigDecimal arithmetic, 4 threads as in
+
+A plain run does only what the headline needs: generate, upload, warm up, time `--steps` pivots, print the line
+(`value`, `ms_per_step` and the roofline of the timed region's own launches).  Everything else runs with `--full`:
+`parity_after_timed_region` (warm-up + steps pivots replayed on the fp64 oracle and compared bit for bit with what the
+timed handle holds), `cpu_baseline` = the decimal-15 oracle (the reference's BigDecimal arithmetic, 4 threads as in
 pivotConcurrently) and `cpu_baseline_fp64` = the fp64 oracle on all host cores, both timed here on a bounded
-row-sample of the same tableau.  At N=1 the line also carries a `cfg3` object (BASELINE's single-GPU roofline config).
+row-sample of the same tableau; at N=1 the `cfg3` object (BASELINE's single-GPU roofline config), the `steady`,
+`steady_plain` / `steady_fused` and `onepass` legs and extra roofline sampling calls of a short command; at N>1 the
+lpx_multi self-check and the `onepass`, `onehop`, `onehop_grid` and `ref_1gpu` legs.  The `--no-*` options leave
+single pieces of a `--full` run out.
+
+`--dump-outputs DIR` writes what the timed loop leaves a caller after its last step as DIR/<name>.npy, float64 (see
+dump_outputs); the inputs depend on --workload and --seed only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -219,6 +228,29 @@ def gen_rows(m, n, seed, r0, r1):
     return A, b, c
 
 
+DUMP_SAMPLE_ROWS = 256     # 32 MiB of tableau rows at n = 16384
+
+
+def dump_outputs(out_dir, handle, seed, loop_result):
+    """--dump-outputs: what a caller of the timed loop receives after its last step, as float64 .npy files: the loop's
+    (status, pivots), v, b, c, the basis permutation, the device checksums of A, b and c (each 64-bit word as its high
+    and low 32 bits: covers every entry of the tableau) and a fixed, seeded sample of DUMP_SAMPLE_ROWS tableau rows with
+    their indices (every row when there are fewer).  Reads the state only: the handle is left as it was."""
+    os.makedirs(out_dir, exist_ok=True)
+    # the C ABI reads the tableau back whole (lpx_state_read has no row range): a second host copy of A (4 GiB at cfg4)
+    # for a moment and a few seconds, paid only with --dump-outputs and after the timed region
+    A, b, c, v, perm = handle.read(want_A=True)
+    m = A.shape[0]
+    rows = (np.arange(m) if m <= DUMP_SAMPLE_ROWS else
+            np.sort(np.random.default_rng([seed, 3]).choice(m, DUMP_SAMPLE_ROWS, replace=False)))
+    arrays = {"loop_status_pivots": np.array(loop_result[:2]), "v": np.array([v]), "b": b, "c": c, "perm": perm,
+              "tableau_checksum": np.array([[x >> 32, x & 0xFFFFFFFF] for x in handle.checksum()]),
+              "A_sample_rows": rows, "A_sample": A[rows]}
+    del A
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def host_cores():
     """CPU threads this process may really use: affinity mask and cgroup quota, not the host's core count
     (a GPU box gives one job a 16-CPU share of a much larger host)."""
@@ -311,10 +343,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--workload", default=os.environ.get("LPX_BENCH_WORKLOAD", "cfg4"), choices=sorted(WORKLOADS))
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement and check of the line: oracle replays, CPU "
+                         "baselines, the cfg3 / steady / fused / one-pass legs (N=1), the multi-GPU self-check and legs "
+                         "(N>1); the --no-* options below leave single pieces of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed loop leaves a caller (v, b, c, perm, checksums of "
+                         "the tableau, a seeded sample of its rows) as DIR/<name>.npy in float64 (rccl form: rank 0's rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cfg3", action="store_true",
                     help="N=1, cfg4: skip the extra `cfg3` object (BASELINE.md quotes its single-GPU roofline target on "
-                         "cfg3, so it is measured in the same run by default; a profile of ONE workload wants it off)")
+                         "cfg3, so a --full run measures it by default; a profile of ONE workload wants it off)")
     ap.add_argument("--no-steady", action="store_true",
                     help="N=1, cfg4: skip the `steady` object (the default loop for --steady-steps pivots after "
                          "--steady-warmup, cfg4 and cfg3, added when the headline run itself is shorter than that)")
@@ -361,6 +400,9 @@ def main():
                     help="N=1: run the lpx_multi path with this many shards, all on this GPU (peer-to-self rehearsal; "
                          "needs GPU_MAX_HW_QUEUES >= shards in the environment)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the outputs and the line; nothing else
+        args.no_cpu_baseline = args.no_cfg3 = args.no_steady = args.no_fused = args.no_onepass = args.no_parity = True
 
     # The contract is ONE JSON line on stdout: RCCL prints a version banner to fd 1 at init, so everything
     # else (C-level output included) is routed to stderr and the JSON line goes to the saved descriptor.
@@ -435,10 +477,11 @@ def main():
             return bool(inf["arith_fused"])
         return options.get("fused", 0) == 1
 
-    def run_single(Aw, bw, cw, mw, nw, steps=None, warmup=None, st=None, done=0, opts=None):
+    def run_single(Aw, bw, cw, mw, nw, steps=None, warmup=None, st=None, done=0, opts=None, after_timed=None):
         """warm-up + timed region of the single-GPU device loop on one workload; returns the measurements.
         st: continue on this handle (it has done `done` pivots) instead of uploading the tableau again.
-        opts: the handle's options (default: the --option set)."""
+        opts: the handle's options (default: the --option set).
+        after_timed: called with the handle and the timed loop's (status, pivots) right behind the timed region."""
         Ks = K if steps is None else steps
         Ws = W if warmup is None else warmup
         t_up = time.perf_counter()
@@ -457,8 +500,10 @@ def main():
         elapsed = time.perf_counter() - t0
         launches, kernel_ms = st.profile_read()
         assert piv == Ks, "timed region did %d pivots instead of %d (status %d)" % (piv, Ks, status)
+        if after_timed is not None:
+            after_timed(st, (status, piv))
         extra_calls = 0
-        if block > 1 and 0 < launches < 3 and args.event_every > 0:
+        if args.full and block > 1 and 0 < launches < 3 and args.event_every > 0:
             # the roofline figure of a short command (the driver's 20 steps are ONE sweep launch) rests on at least three
             # launches: the same budget again, outside the timed region, same kernel, same padding (Weak 8)
             while launches < 3 and extra_calls < 4:
@@ -532,7 +577,7 @@ def main():
         if rank == 0:
             try:
                 devices = list(range(world)) if world > 1 else [local_rank] * nshards
-                if world > 1:
+                if world > 1 and args.full:
                     peer_selfcheck(devices)
                 t_up = time.perf_counter()
                 mt = LPMulti(Aw, bw, cw, devices=devices, options=options)
@@ -552,6 +597,8 @@ def main():
                 err = "%s: %s" % (type(ex).__name__, ex)
         barrier()
         elapsed = time.perf_counter() - t0
+        if rank == 0 and err is None and args.dump_outputs:
+            dump_outputs(args.dump_outputs, mt, args.seed, (status, piv))
         onepass, onehop, grid_leg, ref_1gpu = None, None, None, None
         counted = [0]               # pivots done behind the timed region, counted as they are done (the replay covers them)
 
@@ -699,7 +746,8 @@ def main():
         pivots_per_launch, t_up, info = r1_["pivots_per_launch"], r1_["upload_s"], r1_["info"]
         objective = st.v if rank == 0 else None
     elif not sharded:
-        r1_ = run_single(A, b, c, m, n)
+        r1_ = run_single(A, b, c, m, n, after_timed=(lambda h, res: dump_outputs(args.dump_outputs, h, args.seed, res))
+                         if args.dump_outputs else None)
         eng = st = r1_["st"]
         elapsed, block, launches, avg_ms = r1_["elapsed"], r1_["block"], r1_["launches"], r1_["avg_ms"]
         pivots_per_launch, t_up, info = r1_["pivots_per_launch"], r1_["upload_s"], r1_["info"]
@@ -728,6 +776,8 @@ def main():
         elapsed = time.perf_counter() - t0
         launches, kernel_ms = eng.profile_read()
         eng.profile_enable(False)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, eng, args.seed, (status, piv))
         objective = eng.read(want_A=False)[3]
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -15,8 +15,10 @@ NTs = [int(x) for x in os.environ.get("SWEEP_NT", "0,1").split(",")]
 rows = []
 for U, R, NT in itertools.product(Us, Rs, NTs):
     env = dict(os.environ, LPX_U=str(U), LPX_ROWS_PER_TILE=str(R), LPX_NT=str(NT))
+    # --full: the roofline rests on >= 3 sampled launches (a 60-step call at blocks of 64 is one sweep)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "60",
-                        "--warmup", "5", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
+                        "--warmup", "5", "--full", "--no-cpu-baseline"],
+                       env=env, capture_output=True, text=True, timeout=300)
     try:
         j = json.loads(p.stdout.strip().splitlines()[-1])
         rows.append((U, R, NT, j["roofline"]["achieved"], j["roofline"]["avg_kernel_ms"], j["value"]))

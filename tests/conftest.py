@@ -11,9 +11,16 @@ import pytest
 
 # The multi-device path is rehearsed on ONE GPU (every shard on device 0): its persistent decision kernels wait for each
 # other, so each needs a hardware queue of its own.  The HIP runtime maps streams onto 4 hardware queues by default;
-# this must be set before the runtime initialises (i.e. before torch / liblpx touch the GPU).  On a real multi-GPU
-# node every device has its own queues and nothing needs to be set.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# this must be set before the runtime initialises (i.e. before torch / liblpx touch the GPU).  An environment that
+# already pins a smaller value (the runtime's default of 4 set explicitly, say) is raised: four shards of one tableau
+# on one GPU then share queues and their decision kernels can wait on each other until the spin bound ends the loop.
+# On a real multi-GPU node every device has its own queues and nothing needs to be set.
+try:
+    _hw_queues = int(os.environ.get("GPU_MAX_HW_QUEUES", ""))
+except ValueError:
+    _hw_queues = 0
+if _hw_queues < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

@@ -1,6 +1,8 @@
 """The pure helpers behind bench.py's JSON line: the bounded roofline of one sweep launch and which half of the blocked
-loop sets the pace (no GPU, no library)."""
+loop sets the pace, and the files --dump-outputs writes (no GPU, no library)."""
 import math
+
+import numpy as np
 
 import bench
 
@@ -57,3 +59,58 @@ def test_loop_bound_names_the_slower_half():
     assert bench.loop_bound(1.87 / 20, 20, 1.40, {"overlapped": 0})["bound"].startswith("serial")
     # one pass per pivot has no second half
     assert bench.loop_bound(1.36, 1, 1.36, None) is None
+
+
+class _FakeHandle:
+    """What dump_outputs needs of a handle: read() and checksum(), as LPState / LPMulti / HipShardEngine give them."""
+
+    def __init__(self, m, n):
+        rng = np.random.default_rng(4)
+        self.A, self.b, self.c = rng.random((m, n)), rng.random(m), rng.random(n)
+        self.perm = np.arange(n + m, dtype=np.int32)[::-1].copy()
+
+    def read(self, want_A=True):
+        return (self.A.copy() if want_A else None), self.b.copy(), self.c.copy(), 12.5, self.perm.copy()
+
+    def checksum(self):
+        return (1 << 63) | 5, 7 << 32, 3
+
+
+def test_dump_outputs_writes_float64_and_a_fixed_row_sample(tmp_path):
+    h = _FakeHandle(1000, 64)
+    bench.dump_outputs(str(tmp_path / "a"), h, 1, (9, 40))
+    bench.dump_outputs(str(tmp_path / "b"), h, 1, (9, 40))
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["A_sample.npy", "A_sample_rows.npy", "b.npy", "c.npy", "loop_status_pivots.npy", "perm.npy",
+                     "tableau_checksum.npy", "v.npy"]
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert all(a.dtype == np.float64 for a in got.values())
+    for name, a in got.items():      # same seed, same state: the same files
+        assert np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy"))), name
+    rows = got["A_sample_rows"].astype(np.int64)
+    assert len(rows) == bench.DUMP_SAMPLE_ROWS and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["A_sample"], h.A[rows])
+    assert np.array_equal(got["perm"], h.perm) and got["v"].tolist() == [12.5]
+    assert got["loop_status_pivots"].tolist() == [9, 40]
+    # every 64-bit checksum word survives as two exact 32-bit halves
+    assert [int(hi) << 32 | int(lo) for hi, lo in got["tableau_checksum"]] == list(h.checksum())
+    # fewer rows than the sample: all of them
+    bench.dump_outputs(str(tmp_path / "c"), _FakeHandle(10, 8), 1, (9, 1))
+    assert np.load(tmp_path / "c" / "A_sample_rows.npy").tolist() == list(range(10))
+
+
+def test_dump_outputs_stays_under_64_mb_at_cfg4(tmp_path):
+    # the files dump_outputs writes for cfg4's width at two heights above the row sample; what grows with the height
+    # (b, perm) is scaled up to cfg4's 32768 rows
+    m, n = bench.WORKLOADS["cfg4"]
+
+    def written(rows):
+        d = tmp_path / str(rows)
+        bench.dump_outputs(str(d), _FakeHandle(rows, n), 1, (9, 1024))
+        return sum(p.stat().st_size for p in d.iterdir())
+
+    lo, hi = bench.DUMP_SAMPLE_ROWS + 44, 2 * bench.DUMP_SAMPLE_ROWS + 88
+    small, large = written(lo), written(hi)
+    per_row = (large - small) / float(hi - lo)
+    assert 0 < per_row <= 16           # b and perm: one float64 each per row
+    assert small + (m - lo) * per_row < 64e6
