@@ -374,6 +374,62 @@ int lpx_solve_multi(int32_t m, int32_t n, const double* A, int64_t lda, const do
                     int32_t maximize, const lpx_solve_options* opts, const int32_t* devices, int32_t n_dev,
                     lpx_solve_result* result);
 
+/* ------------------------------------------------------------------------------------------------
+ * Many small LPs in one launch: `count` independent LPStates, ONE workgroup per LP, the LP's whole state (A, b, c, v,
+ * perm) in the LDS of its CU for the whole loop of LPSolver.simplex — no launch, no HBM traffic and no host decision
+ * per pivot.  For scenario sweeps, branch-and-bound nodes, per-sample LPs: thousands of LPs of some 10..100 rows and
+ * columns, where the one-tableau path above leaves 255 of 256 CUs idle.  Shapes may differ inside a batch.  Results are
+ * bit-identical to an lpx_state driven over the same LP, in both arithmetic modes.
+ * ---------------------------------------------------------------------------------------------- */
+#define LPX_BATCH_LDS_BYTES 163840
+/* Host-only: LDS bytes one m x n LP needs in the batch kernel; an LP fits iff the value is <= LPX_BATCH_LDS_BYTES.
+ * With ld = n | 1 (odd row pitch) and ev(x) = x rounded up to even:
+ *   8 * ( ev(m*ld + m + n + 1) + ev(ceil((n + m) / 2)) + ev(m) ) + 512
+ * — the image A | b | c | v | perm, the saved entering column, the reduction scratch.  64 x 64: 35 856 (four per CU);
+ * the largest LP with 200 columns has 98 rows.  Negative m or n: -1. */
+int64_t lpx_batch_lds_bytes(int32_t m, int32_t n);
+
+typedef struct lpx_batch lpx_batch;
+/* new LPState(A, b, c, v, variables, coefficients, m, n), `count` times   LPState.java:88-112
+ * Shapes m[k] x n[k] <= m_max x n_max (m and n both NULL: every LP is m_max x n_max).  LP k reads
+ * A + k*strideA (row-major, leading dimension lda >= n_max), b + k*m_max, c + k*n_max, v[k] (v NULL: 0) and the first
+ * n[k] + m[k] entries of perm + k*(n_max + m_max) (perm NULL: identity).  HOST arrays, copied.  An LP that does not fit
+ * the LDS of one workgroup, a negative count, dimension or stride, lda < n_max or a NULL array where data is due give
+ * LPX_BAD_ARGUMENT (lpx_last_error names the LP and its shape) before any device call. */
+int lpx_batch_create(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n,
+                     const double* A, int64_t lda, int64_t strideA, const double* b, const double* c,
+                     const double* v, const int32_t* perm, int device, lpx_batch** out);
+void lpx_batch_destroy(lpx_batch* s);
+/* LPX_OPT_FUSED only: 0 = two roundings per update, 1 = fused multiply-add, 2 = by size, which is 0 for every LP that
+ * fits a batch.  As on an lpx_state: set it before the first pivot. */
+int lpx_batch_set_option(lpx_batch* s, int32_t key, int64_t value);
+/* Entering rule of every LP of the batch, as lpx_state_set_pricing (0 = the reference's rule, 1 = Dantzig). */
+int lpx_batch_set_pricing(lpx_batch* s, int32_t pricing);
+/* The loop of LPSolver.simplex                                         LPSolver.java:101-107
+ * lpx_simplex_loop for every LP of the batch, in ONE launch: pivots_done[count], status[count] (LPX_OPTIMAL |
+ * LPX_UNBOUNDED | LPX_PIVOT_LIMIT per LP); max_pivots (<0: unlimited) is the budget of EACH LP.  track_slot[count]
+ * (or NULL) follows one slot per LP through the pivots as solveAuxLP does for x0 (LPSolver.java:151-155), in and out;
+ * -1 = none for that LP.  The states stay on the device: a later call resumes from them. */
+int lpx_batch_simplex_loop(lpx_batch* s, int64_t max_pivots, int64_t* pivots_done, int32_t* status, int32_t* track_slot);
+/* Read-back of LP `index` as lpx_state_read (host pointers, any may be NULL; A row-major with leading dimension lda >= n). */
+int lpx_batch_read(lpx_batch* s, int32_t index, double* A, int64_t lda, double* b, double* c, double* v, int32_t* perm);
+int lpx_batch_count(const lpx_batch* s);
+/* BigDecimal LPSolver.solve(LPStandardForm stForm), `count` times        LPSolver.java:78
+ * Standard forms laid out as for lpx_batch_create; maximize[count].  results[k] is what lpx_solve fills for LP k alone
+ * (status, phase1_used, objective, objective_text, objective_rounded, pivot counts, x0_slot); seconds_total and
+ * seconds_pivots hold the times of the WHOLE call in every entry.  The forms that need no phase 1 (min b >= 0,
+ * LPSolver.java:119) are solved together by one launch of the batch kernel; a form that needs the auxiliary LP is
+ * solved on its own through lpx_solve, into the same results array.  *n_in_batch (may be NULL) receives how many took
+ * the batch kernel.  Honoured options: device, max_pivots, pricing, fused (0 = the library's choice by size = two
+ * roundings at these sizes, as in lpx_solve), and restore_order / restore_order_len, which are handed to lpx_solve
+ * unchanged; keep_state, perm_out and x_out must be NULL.  Every LP must fit the batch kernel (lpx_batch_lds_bytes).
+ * Returns 0 when the call itself worked — an unbounded or infeasible LP is reported in its results[k].status only —
+ * LPX_BAD_ARGUMENT or LPX_DEVICE_ERROR otherwise. */
+int lpx_solve_batch(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n,
+                    const double* A, int64_t lda, int64_t strideA, const double* b, const double* c,
+                    const int32_t* maximize, const lpx_solve_options* opts, lpx_solve_result* results,
+                    int32_t* n_in_batch);
+
 /* LPState restoreInitialLP(auxLP, initial, indexOfX0)                   LPSolver.java:200-246
  * In place on the auxiliary-LP handle (m x (n+1), as left by phase 1): drops x0's column, rebuilds c and v by
  * substitution in keySet() order (`order`, order_len <= n original-variable indices; NULL = default-name order of all n), renumbers

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("LPX_LIB_PATH") or os.path.join(_HERE, "liblpx.so")
 OPTIMAL, UNBOUNDED, INFEASIBLE, AUX_UNBOUNDED, NO_DEGENERATE_PIVOT, BAD_ARGUMENT, RESTORE_INDEX_FAULT, \
     DEVICE_ERROR, DIVIDE_BY_ZERO, PIVOT_LIMIT = range(10)
 CAND_HEADER = 8
+BATCH_LDS_BYTES = 163840   # LPX_BATCH_LDS_BYTES
 PRICING = {"reference": 0, "first-positive": 0, "dantzig": 1, 0: 0, 1: 1}
 
 # lpx_option (include/lpx.h)
@@ -147,6 +148,17 @@ SYMBOLS = [
     ("lpx_restore_initial_lp", C.c_int, [C.c_void_p, dp, C.c_int32, C.c_int32, ip, C.c_int32]),
     ("lpx_java_default_name_order", C.c_int, [C.c_int32, ip]),
     ("lpx_transpose", C.c_int, [C.c_int32, C.c_int32, dp, C.c_int64, dp, C.c_int64, C.c_int]),
+    ("lpx_batch_lds_bytes", C.c_int64, [C.c_int32, C.c_int32]),
+    ("lpx_batch_create", C.c_int, [C.c_int32, C.c_int32, C.c_int32, ip, ip, dp, C.c_int64, C.c_int64, dp, dp, dp, ip,
+                                   C.c_int, C.POINTER(C.c_void_p)]),
+    ("lpx_batch_destroy", None, [C.c_void_p]),
+    ("lpx_batch_set_option", C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
+    ("lpx_batch_set_pricing", C.c_int, [C.c_void_p, C.c_int32]),
+    ("lpx_batch_simplex_loop", C.c_int, [C.c_void_p, C.c_int64, i64p, ip, ip]),
+    ("lpx_batch_read", C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, dp, dp, dp, ip]),
+    ("lpx_batch_count", C.c_int, [C.c_void_p]),
+    ("lpx_solve_batch", C.c_int, [C.c_int32, C.c_int32, C.c_int32, ip, ip, dp, C.c_int64, C.c_int64, dp, dp, ip,
+                                  C.POINTER(SolveOptions), C.POINTER(SolveResult), ip]),
 ]
 
 _lib = None

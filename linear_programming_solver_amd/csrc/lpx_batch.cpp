@@ -1,0 +1,385 @@
+// Batched solve behind the C ABI (include/lpx.h): many small LPs in ONE launch of k_batch_simplex (lpx_batch.inc), one
+// workgroup per LP with the LP's whole state in LDS.  The handle keeps one HBM image per LP (lpxk::BatchLayout); every
+// argument is checked before the first device call, so a bad call answers LPX_BAD_ARGUMENT on a machine without a GPU too.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "lpx_internal.h"
+
+namespace lpx_internal {
+void round6_text(double v, char* out, size_t cap);   // lpx_solver.cpp
+}
+
+struct lpx_batch {
+  int device = 0;
+  int32_t count = 0, m_max = 0, n_max = 0;
+  std::vector<int32_t> m, n;
+  std::vector<int64_t> offset;      // first double of LP k's image; offset[count] = doubles of all images
+  int32_t lds_bytes = 0;            // dynamic LDS of the launch: the largest LP's
+  int32_t threads = 64;             // workgroup size chosen for the batch
+  int fused = 0, pricing = 0;
+  hipStream_t stream = nullptr;
+  double* d_image = nullptr;
+  int64_t *d_offset = nullptr, *d_pivots = nullptr;
+  int32_t *d_m = nullptr, *d_n = nullptr, *d_status = nullptr, *d_track = nullptr;
+};
+
+namespace {
+
+double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+int64_t lds_bytes_of(int64_t m, int64_t n) {
+  if (m < 0 || n < 0) return -1;
+  if ((double)m * (double)(n | 1) > 1e12) return INT64_MAX;   // far beyond any LDS; keeps the formula inside int64
+  return lpxk::batch_layout(m, n).lds_bytes;
+}
+
+// Workgroup size of one LP: a wave per 64-column chunk times up to four row groups of at least 16 rows, at most 16
+// waves.  One wave (no workgroup barriers) up to 16 x 64; 256 threads for 64 x 64; 1024 from 64 x 256 or 49 x 200 on.
+int threads_of(int32_t m, int32_t n) {
+  const int nq = std::max(1, (n + 63) / 64);
+  const int groups = std::min(4, std::max(1, (m + 15) / 16));
+  return 64 * std::min(16, nq * groups);
+}
+
+// shapes of a batch: every LP inside m_max x n_max and inside the LDS of one workgroup
+int check_shapes(const char* who, int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n) {
+  if (count < 0 || m_max < 0 || n_max < 0)
+    return fail(LPX_BAD_ARGUMENT, std::string(who) + ": negative count or dimension");
+  if ((m == nullptr) != (n == nullptr)) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": m and n must both be given or both be NULL");
+  for (int32_t k = 0; k < count; k++) {
+    const int32_t mk = m ? m[k] : m_max, nk = n ? n[k] : n_max;
+    char msg[200];
+    if (mk < 0 || nk < 0 || mk > m_max || nk > n_max) {
+      snprintf(msg, sizeof msg, "%s: LP %d has shape %d x %d outside 0..%d x 0..%d", who, k, mk, nk, m_max, n_max);
+      return fail(LPX_BAD_ARGUMENT, msg);
+    }
+    const int64_t need = lds_bytes_of(mk, nk);
+    if (need > LPX_BATCH_LDS_BYTES) {
+      snprintf(msg, sizeof msg, "%s: LP %d of shape %d x %d needs %lld bytes of LDS, a workgroup has %d", who, k, mk, nk,
+               (long long)need, LPX_BATCH_LDS_BYTES);
+      return fail(LPX_BAD_ARGUMENT, msg);
+    }
+  }
+  return 0;
+}
+
+int check_arrays(const char* who, int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n,
+                 const double* A, int64_t lda, int64_t strideA, const double* b, const double* c) {
+  bool needA = false, needb = false, needc = false;
+  for (int32_t k = 0; k < count; k++) {
+    const int32_t mk = m ? m[k] : m_max, nk = n ? n[k] : n_max;
+    needA |= mk > 0 && nk > 0;
+    needb |= mk > 0;
+    needc |= nk > 0;
+  }
+  if (lda < n_max || strideA < 0) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": lda < n_max or negative strideA");
+  if ((needA && !A) || (needb && !b) || (needc && !c)) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL array where data is due");
+  return 0;
+}
+
+void free_batch(lpx_batch* B) {
+  if (!B) return;
+  if (B->stream || B->d_image || B->d_offset) {
+    (void)hipSetDevice(B->device);
+    (void)hipFree(B->d_image);
+    (void)hipFree(B->d_offset);
+    (void)hipFree(B->d_pivots);
+    (void)hipFree(B->d_m);
+    (void)hipFree(B->d_n);
+    (void)hipFree(B->d_status);
+    (void)hipFree(B->d_track);
+    if (B->stream) (void)hipStreamDestroy(B->stream);
+  }
+  delete B;
+}
+
+struct BatchGuard {
+  lpx_batch* B = nullptr;
+  ~BatchGuard() { free_batch(B); }
+};
+
+// the checked core of lpx_batch_create (no argument checks: the callers have made them)
+int create_checked(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n, const double* A,
+                   int64_t lda, int64_t strideA, const double* b, const double* c, const double* v, const int32_t* perm,
+                   int device, lpx_batch** out) {
+  BatchGuard guard;
+  lpx_batch* B = guard.B = new lpx_batch();
+  B->device = device;
+  B->count = count;
+  B->m_max = m_max;
+  B->n_max = n_max;
+  B->m.resize(count);
+  B->n.resize(count);
+  B->offset.resize((size_t)count + 1);
+  int64_t total = 0, lds = 0;
+  int threads = 64;
+  for (int32_t k = 0; k < count; k++) {
+    B->m[k] = m ? m[k] : m_max;
+    B->n[k] = n ? n[k] : n_max;
+    const lpxk::BatchLayout L = lpxk::batch_layout(B->m[k], B->n[k]);
+    B->offset[k] = total;
+    total += L.image;
+    lds = std::max(lds, L.lds_bytes);
+    threads = std::max(threads, threads_of(B->m[k], B->n[k]));
+  }
+  B->offset[count] = total;
+  B->lds_bytes = (int32_t)lds;
+  B->threads = threads;
+  std::vector<double> img((size_t)total, 0.0);
+  for (int32_t k = 0; k < count; k++) {
+    const int32_t mk = B->m[k], nk = B->n[k];
+    const lpxk::BatchLayout L = lpxk::batch_layout(mk, nk);
+    double* g = img.data() + B->offset[k];
+    for (int32_t i = 0; i < mk; i++)
+      if (nk > 0) memcpy(g + (int64_t)i * L.ld, A + (int64_t)k * strideA + (int64_t)i * lda, (size_t)nk * sizeof(double));
+    if (mk > 0) memcpy(g + L.b, b + (int64_t)k * m_max, (size_t)mk * sizeof(double));
+    if (nk > 0) memcpy(g + L.c, c + (int64_t)k * n_max, (size_t)nk * sizeof(double));
+    g[L.v] = v ? v[k] : 0.0;
+    int32_t* p = (int32_t*)(g + L.perm);
+    for (int32_t s = 0; s < nk + mk; s++) p[s] = perm ? perm[(int64_t)k * ((int64_t)n_max + m_max) + s] : s;
+  }
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreateWithFlags(&B->stream, hipStreamNonBlocking));
+  const size_t cnt = (size_t)std::max(count, 1);
+  HIP_TRY(hipMalloc((void**)&B->d_image, std::max<size_t>((size_t)total, 2) * sizeof(double)));
+  HIP_TRY(hipMalloc((void**)&B->d_offset, cnt * sizeof(int64_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_pivots, cnt * sizeof(int64_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_m, cnt * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_n, cnt * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_status, cnt * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_track, cnt * sizeof(int32_t)));
+  if (total > 0) HIP_TRY(hipMemcpyAsync(B->d_image, img.data(), (size_t)total * sizeof(double), hipMemcpyHostToDevice, B->stream));
+  if (count > 0) {
+    HIP_TRY(hipMemcpyAsync(B->d_offset, B->offset.data(), (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, B->stream));
+    HIP_TRY(hipMemcpyAsync(B->d_m, B->m.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+    HIP_TRY(hipMemcpyAsync(B->d_n, B->n.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(B->stream));   // img goes out of scope
+  guard.B = nullptr;
+  *out = B;
+  return 0;
+}
+
+// LPX_BATCH_THREADS (debugging aid of scripts/bench_batch.py, read at every loop call): workgroup size instead of the
+// by-size choice, rounded down to a multiple of 64 inside 64..1024
+int threads_in_effect(const lpx_batch* B) {
+  const char* e = getenv("LPX_BATCH_THREADS");
+  if (e && *e) {
+    const int t = atoi(e);
+    if (t > 0) return std::max(64, std::min(1024, t / 64 * 64));
+  }
+  return B->threads;
+}
+
+}  // namespace
+
+extern "C" int64_t lpx_batch_lds_bytes(int32_t m, int32_t n) {
+  const int64_t r = lds_bytes_of(m, n);
+  if (r < 0) fail(LPX_BAD_ARGUMENT, "lpx_batch_lds_bytes: negative dimension");
+  return r;
+}
+
+extern "C" int lpx_batch_create(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n,
+                                const double* A, int64_t lda, int64_t strideA, const double* b, const double* c,
+                                const double* v, const int32_t* perm, int device, lpx_batch** out) {
+  if (!out) return fail(LPX_BAD_ARGUMENT, "lpx_batch_create: out is NULL");
+  *out = nullptr;
+  if (int rc = check_shapes("lpx_batch_create", count, m_max, n_max, m, n)) return rc;
+  if (int rc = check_arrays("lpx_batch_create", count, m_max, n_max, m, n, A, lda, strideA, b, c)) return rc;
+  if (device < 0) return fail(LPX_BAD_ARGUMENT, "lpx_batch_create: negative device");
+  DeviceRestore keep_device;
+  return create_checked(count, m_max, n_max, m, n, A, lda, strideA, b, c, v, perm, device, out);
+}
+
+extern "C" void lpx_batch_destroy(lpx_batch* B) {
+  DeviceRestore keep_device;
+  free_batch(B);
+}
+
+extern "C" int lpx_batch_count(const lpx_batch* B) { return B ? B->count : 0; }
+
+extern "C" int lpx_batch_set_option(lpx_batch* B, int32_t key, int64_t value) {
+  if (!B) return fail(LPX_BAD_ARGUMENT, "lpx_batch_set_option: NULL handle");
+  if (key != LPX_OPT_FUSED || value < 0 || value > 2)
+    return fail(LPX_BAD_ARGUMENT, "lpx_batch_set_option: only LPX_OPT_FUSED (0, 1, 2) applies to a batch");
+  B->fused = value == 1;   // 2 = by size: every LP of a batch is far below the switch, i.e. 0
+  return 0;
+}
+
+extern "C" int lpx_batch_set_pricing(lpx_batch* B, int32_t pricing) {
+  if (!B || (pricing != 0 && pricing != 1)) return fail(LPX_BAD_ARGUMENT, "lpx_batch_set_pricing: bad argument");
+  B->pricing = pricing;
+  return 0;
+}
+
+extern "C" int lpx_batch_simplex_loop(lpx_batch* B, int64_t max_pivots, int64_t* pivots_done, int32_t* status,
+                                      int32_t* track_slot) {
+  if (!B) return fail(LPX_BAD_ARGUMENT, "lpx_batch_simplex_loop: NULL handle");
+  if (B->count > 0 && (!pivots_done || !status)) return fail(LPX_BAD_ARGUMENT, "lpx_batch_simplex_loop: NULL output array");
+  if (B->count == 0) return 0;
+  if (track_slot)
+    for (int32_t k = 0; k < B->count; k++)
+      if (track_slot[k] < -1 || track_slot[k] >= B->n[k] + B->m[k])
+        return fail(LPX_BAD_ARGUMENT, "lpx_batch_simplex_loop: tracked slot " + std::to_string(track_slot[k]) + " of LP " +
+                                          std::to_string(k) + " is outside its n + m slots");
+  DeviceRestore keep_device;
+  HIP_TRY(hipSetDevice(B->device));
+  const size_t cnt = (size_t)B->count;
+  if (track_slot) HIP_TRY(hipMemcpyAsync(B->d_track, track_slot, cnt * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+  else HIP_TRY(hipMemsetAsync(B->d_track, 0xff, cnt * sizeof(int32_t), B->stream));   // -1: nothing tracked
+  lpxk::BatchArgs a{};
+  a.count = B->count;
+  a.m = B->d_m;
+  a.n = B->d_n;
+  a.offset = B->d_offset;
+  a.image = B->d_image;
+  a.pivots = B->d_pivots;
+  a.status = B->d_status;
+  a.track = B->d_track;
+  a.max_pivots = max_pivots;
+  a.dantzig = B->pricing == 1;
+  a.fused = B->fused;
+  a.lds_bytes = B->lds_bytes;
+  a.threads = threads_in_effect(B);
+  HIP_TRY(lpxk::launch_batch_simplex(a, B->stream));
+  HIP_TRY(hipMemcpyAsync(pivots_done, B->d_pivots, cnt * sizeof(int64_t), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipMemcpyAsync(status, B->d_status, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, B->stream));
+  if (track_slot) HIP_TRY(hipMemcpyAsync(track_slot, B->d_track, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipStreamSynchronize(B->stream));
+  return 0;
+}
+
+extern "C" int lpx_batch_read(lpx_batch* B, int32_t index, double* A, int64_t lda, double* b, double* c, double* v,
+                              int32_t* perm) {
+  if (!B || index < 0 || index >= B->count) return fail(LPX_BAD_ARGUMENT, "lpx_batch_read: bad handle or index");
+  const int32_t mk = B->m[index], nk = B->n[index];
+  if (A && lda < nk) return fail(LPX_BAD_ARGUMENT, "lpx_batch_read: lda < n");
+  const lpxk::BatchLayout L = lpxk::batch_layout(mk, nk);
+  std::vector<double> img((size_t)L.image);
+  DeviceRestore keep_device;
+  HIP_TRY(hipSetDevice(B->device));
+  HIP_TRY(hipMemcpyAsync(img.data(), B->d_image + B->offset[index], img.size() * sizeof(double), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipStreamSynchronize(B->stream));
+  if (A && nk > 0)
+    for (int32_t i = 0; i < mk; i++) memcpy(A + (int64_t)i * lda, img.data() + (int64_t)i * L.ld, (size_t)nk * sizeof(double));
+  if (b && mk > 0) memcpy(b, img.data() + L.b, (size_t)mk * sizeof(double));
+  if (c && nk > 0) memcpy(c, img.data() + L.c, (size_t)nk * sizeof(double));
+  if (v) *v = img[L.v];
+  if (perm && nk + mk > 0) memcpy(perm, img.data() + L.perm, ((size_t)nk + mk) * sizeof(int32_t));
+  return 0;
+}
+
+// What the launch of this handle looks like (scripts/bench_batch.py): not part of include/lpx.h
+extern "C" int lpxi_batch_launch_info(lpx_batch* B, int32_t* threads, int32_t* lds_bytes, int32_t* blocks_per_cu) {
+  if (!B) return fail(LPX_BAD_ARGUMENT, "lpxi_batch_launch_info: NULL handle");
+  DeviceRestore keep_device;
+  HIP_TRY(hipSetDevice(B->device));
+  const int t = threads_in_effect(B);
+  if (threads) *threads = t;
+  if (lds_bytes) *lds_bytes = B->lds_bytes;
+  if (blocks_per_cu) *blocks_per_cu = lpxk::batch_blocks_per_cu(t, B->lds_bytes);
+  return 0;
+}
+
+// LPSolver.solve (LPSolver.java:78) for `count` standard forms.  The forms with min b >= 0 (no phase 1, :119) become one
+// batch: c negated for `min` on a private copy (:86-89), slack form with the identity permutation (:248-272), ONE launch
+// of the loop (:96-114).  The others take lpx_solve one by one (auxiliary LP, restoreInitialLP), into the same results.
+extern "C" int lpx_solve_batch(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n,
+                               const double* A, int64_t lda, int64_t strideA, const double* b, const double* c,
+                               const int32_t* maximize, const lpx_solve_options* opts, lpx_solve_result* results,
+                               int32_t* n_in_batch) {
+  if (n_in_batch) *n_in_batch = 0;
+  if (int rc = check_shapes("lpx_solve_batch", count, m_max, n_max, m, n)) return rc;
+  if (int rc = check_arrays("lpx_solve_batch", count, m_max, n_max, m, n, A, lda, strideA, b, c)) return rc;
+  if (count > 0 && (!results || !maximize)) return fail(LPX_BAD_ARGUMENT, "lpx_solve_batch: results or maximize is NULL");
+  lpx_solve_options o{};
+  o.max_pivots = -1;
+  if (opts) o = *opts;
+  if (o.keep_state || o.perm_out || o.x_out)
+    return fail(LPX_BAD_ARGUMENT, "lpx_solve_batch: keep_state, perm_out and x_out must be NULL");
+  if (o.device < 0 || (o.pricing != 0 && o.pricing != 1)) return fail(LPX_BAD_ARGUMENT, "lpx_solve_batch: bad device or pricing");
+  const double t_start = now_s();
+  for (int32_t k = 0; k < count; k++) {
+    memset(&results[k], 0, sizeof results[k]);
+    results[k].x0_slot = -1;
+    results[k].status = LPX_BAD_ARGUMENT;
+  }
+  // which forms need no phase 1: minInB (:375-386) finds nothing below 0
+  std::vector<int32_t> in_batch, alone;
+  for (int32_t k = 0; k < count; k++) {
+    const int32_t mk = m ? m[k] : m_max;
+    const double* bk = mk > 0 ? b + (int64_t)k * m_max : nullptr;
+    double mn = 1e50;
+    int idx = -1;
+    for (int i = 0; i < mk; i++)
+      if (mn > bk[i]) { mn = bk[i]; idx = i; }
+    (idx == -1 || bk[idx] >= 0.0 ? in_batch : alone).push_back(k);
+  }
+  double t_pivots = 0.0;
+  const int32_t nb = (int32_t)in_batch.size();
+  if (nb > 0) {
+    // gather the batch: shapes, A rows in place (lda, strideA), b, and c0 = +-c
+    std::vector<int32_t> bm(nb), bn(nb);
+    std::vector<double> bb((size_t)nb * m_max, 0.0), bc((size_t)nb * n_max, 0.0), bA;
+    const int64_t ldp = std::max(n_max, 1), strideP = (int64_t)m_max * ldp;
+    bA.assign((size_t)nb * strideP, 0.0);
+    for (int32_t t = 0; t < nb; t++) {
+      const int32_t k = in_batch[t];
+      bm[t] = m ? m[k] : m_max;
+      bn[t] = n ? n[k] : n_max;
+      for (int32_t i = 0; i < bm[t]; i++)
+        if (bn[t] > 0) memcpy(&bA[(size_t)t * strideP + (size_t)i * ldp], A + (int64_t)k * strideA + (int64_t)i * lda, (size_t)bn[t] * sizeof(double));
+      for (int32_t i = 0; i < bm[t]; i++) bb[(size_t)t * m_max + i] = b[(int64_t)k * m_max + i];
+      for (int32_t j = 0; j < bn[t]; j++) bc[(size_t)t * n_max + j] = maximize[k] ? c[(int64_t)k * n_max + j] : -c[(int64_t)k * n_max + j];
+    }
+    DeviceRestore keep_device;
+    BatchGuard guard;
+    if (int rc = create_checked(nb, m_max, n_max, bm.data(), bn.data(), bA.data(), ldp, strideP, bb.data(), bc.data(), nullptr,
+                                nullptr, o.device, &guard.B))
+      return rc;
+    guard.B->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
+    guard.B->pricing = o.pricing;
+    std::vector<int64_t> done(nb);
+    std::vector<int32_t> st(nb);
+    const double t0 = now_s();
+    if (int rc = lpx_batch_simplex_loop(guard.B, o.max_pivots < 0 ? -1 : o.max_pivots, done.data(), st.data(), nullptr)) return rc;
+    t_pivots = now_s() - t0;
+    std::vector<double> img((size_t)guard.B->offset[nb]);
+    if (!img.empty()) HIP_TRY(hipMemcpy(img.data(), guard.B->d_image, img.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int32_t t = 0; t < nb; t++) {
+      lpx_solve_result& r = results[in_batch[t]];
+      double v = img[(size_t)guard.B->offset[t] + lpxk::batch_layout(bm[t], bn[t]).v];
+      if (!maximize[in_batch[t]]) v = -v;                                             // :90
+      r.objective = v;
+      lpx_internal::round6_text(v, r.objective_text, sizeof r.objective_text);      // :113
+      r.objective_rounded = strtod(r.objective_text, nullptr);
+      r.pivots_phase2 = done[t];
+      r.status = st[t];
+    }
+  }
+  if (n_in_batch) *n_in_batch = nb;
+  lpx_solve_options oa = o;
+  for (int32_t k : alone) {
+    const int rc = lpx_solve(m ? m[k] : m_max, n ? n[k] : n_max, A ? A + (int64_t)k * strideA : nullptr, lda,
+                             b ? b + (int64_t)k * m_max : nullptr, c ? c + (int64_t)k * n_max : nullptr, maximize[k], &oa,
+                             &results[k]);
+    if (rc == LPX_DEVICE_ERROR || rc == LPX_BAD_ARGUMENT) return rc;
+    t_pivots += results[k].seconds_pivots;
+  }
+  const double t_total = now_s() - t_start;
+  for (int32_t k = 0; k < count; k++) {
+    results[k].seconds_total = t_total;
+    results[k].seconds_pivots = t_pivots;
+  }
+  return 0;
+}

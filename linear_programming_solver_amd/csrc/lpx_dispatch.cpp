@@ -82,6 +82,12 @@ void launch_restore_objective(const Buffers& B, int n, const RestoreEntry* d_ent
 void launch_checksum(const Buffers& B, int m_local, int n, int row0, unsigned long long* d_out3, hipStream_t s) {
   plain::launch_checksum(B, m_local, n, row0, d_out3, s);
 }
+hipError_t launch_batch_simplex(const BatchArgs& a, hipStream_t s) {
+  return a.fused ? fused::launch_batch_simplex(a, s) : plain::launch_batch_simplex(a, s);
+}
+int batch_blocks_per_cu(int threads, int lds_bytes) {
+  return std::min(plain::batch_blocks_per_cu(threads, lds_bytes), fused::batch_blocks_per_cu(threads, lds_bytes));
+}
 void launch_transpose(const double* dA, int64_t lda, double* dAt, int64_t ldat, int m, int n, hipStream_t s) {
   plain::launch_transpose(dA, lda, dAt, ldat, m, n, s);
 }

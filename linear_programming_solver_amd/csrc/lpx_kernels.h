@@ -119,6 +119,45 @@ enum SweepKernel { kSweepNone = 0, kSweepTiles = 1, kSweepMulti = 2, kSweepStead
 struct FixSide { hipStream_t stream; hipEvent_t ready, done, packed; };
 struct RestoreEntry { int32_t is_basic; int32_t index; double k; };  // index = row r (basic) or post-drop slot
 
+// ---- batched solve (lpx_batch.inc / lpx_batch.cpp): many small LPs, one workgroup per LP, the whole state in LDS ----
+// Image of ONE m x n LP, in doubles; the HBM copy and the front of the workgroup's LDS are the same image, so it moves
+// in and out with 16-byte accesses:  A (m rows of pitch ld) | b[m] | c[n] | v | pad to even | perm int32[n + m] | pad to even.
+// ld = n | 1: an odd pitch puts the m entries of a column on different LDS banks.  Behind the image the LDS holds what
+// never leaves the chip: the saved entering column (m doubles, padded to even) and kBatchScratchBytes of reduction scratch.
+constexpr int kBatchLdsMax = 163840;      // LPX_BATCH_LDS_BYTES: what gfx950 gives one workgroup
+constexpr int kBatchScratchBytes = 512;   // 2 x 16 RatioRow: the per-wave partials of the entering and of the leaving reduction
+struct BatchLayout {
+  int64_t ld, b, c, v, perm, image, col;  // offsets in doubles (perm: of its first int32); image = doubles of the HBM image
+  int64_t lds_bytes;
+};
+__host__ __device__ inline BatchLayout batch_layout(int64_t m, int64_t n) {
+  BatchLayout L;
+  L.ld = n | 1;
+  L.b = m * L.ld;
+  L.c = L.b + m;
+  L.v = L.c + n;
+  L.perm = (L.v + 2) & ~(int64_t)1;
+  L.image = L.perm + (((n + m + 1) / 2 + 1) & ~(int64_t)1);
+  L.col = L.image;
+  L.lds_bytes = 8 * (L.image + ((m + 1) & ~(int64_t)1)) + kBatchScratchBytes;
+  return L;
+}
+struct BatchArgs {
+  int32_t count;
+  const int32_t* m;        // [count]
+  const int32_t* n;        // [count]
+  const int64_t* offset;   // [count] first double of LP k's image in `image` (even)
+  double* image;
+  int64_t* pivots;         // [count] out: pivots of this call
+  int32_t* status;         // [count] out: lpx_status
+  int32_t* track;          // [count] in/out: tracked slot, -1 = none
+  int64_t max_pivots;      // per LP; < 0: unlimited
+  int32_t dantzig;
+  int32_t fused;           // which compilation the dispatcher takes
+  int32_t lds_bytes;       // dynamic LDS of the launch: the largest batch_layout(m, n).lds_bytes of the batch
+  int32_t threads;         // workgroup size (multiple of 64, <= 1024)
+};
+
 // ---- launch wrappers --------------------------------------------------------------------------------------------
 // lpx_kernels.hip is compiled twice: plain (one rounding per reference operation) and fused (updates as one FMA).
 namespace plain {

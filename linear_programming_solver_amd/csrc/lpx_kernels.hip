@@ -1523,5 +1523,7 @@ void launch_transpose(const double* dA, int64_t lda, double* dAt, int64_t ldat, 
   hipLaunchKernelGGL(k_transpose, dim3((n + 63) / 64, (m + 63) / 64), dim3(256), 0, s, dA, lda, dAt, ldat, m, n);
 }
 
+#include "lpx_batch.inc"
+
 }  // namespace plain / fused
 }  // namespace lpxk

@@ -69,4 +69,8 @@ void launch_fill_column(double* A, int64_t ld, int m, int col, double value, hip
 void launch_drop_column(double* A, int64_t ld, int m, int n_old, int col, hipStream_t s);
 void launch_restore_objective(const Buffers& B, int n, const RestoreEntry* d_entries, int n_entries, hipStream_t s);
 void launch_checksum(const Buffers& B, int m_local, int n, int row0, unsigned long long* d_out3, hipStream_t s);
+// batched solve: the loop of LPSolver.simplex for a.count LPs in one launch, one workgroup per LP (lpx_batch.inc)
+hipError_t launch_batch_simplex(const BatchArgs& a, hipStream_t s);
+// workgroups of that launch one CU holds at once (occupancy API; 0 on error)
+int batch_blocks_per_cu(int threads, int lds_bytes);
 void launch_transpose(const double* dA, int64_t lda, double* dAt, int64_t ldat, int m, int n, hipStream_t s);

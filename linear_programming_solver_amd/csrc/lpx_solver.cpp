@@ -77,7 +77,8 @@ extern "C" int lpx_java_default_name_order(int32_t n, int32_t* order_out) {
 
 // new BigDecimal(v).setScale(6, RoundingMode.HALF_UP) (LPSolver.java:113) as text: the exact binary value
 // of the double is expanded and the first discarded digit decides.
-static void round6_text(double v, char* out, size_t cap) {
+namespace lpx_internal {
+void round6_text(double v, char* out, size_t cap) {
   static thread_local char buf[1400];
   if (!std::isfinite(v)) { snprintf(out, cap, "%g", v); return; }
   snprintf(buf, sizeof buf, "%.1100f", v);
@@ -99,6 +100,7 @@ static void round6_text(double v, char* out, size_t cap) {
   if (neg && !all_zero) r = "-" + r;  // BigDecimal has no negative zero
   snprintf(out, cap, "%s", r.c_str());
 }
+}  // namespace lpx_internal (lpx_batch.cpp rounds its objectives with the same routine)
 
 // LPSolver.java:375-386
 static int min_in_b(const double* b, int m) {

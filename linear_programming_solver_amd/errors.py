@@ -12,21 +12,29 @@ class SolutionException(LPException):
     """lpsolver.SolutionException extends LPException."""
 
 
-def raise_for_status(status):
-    """Raise what the reference would have thrown for a non-OPTIMAL lpx_status."""
+def exception_for_status(status):
+    """What the reference would have thrown for a non-OPTIMAL lpx_status, as an exception INSTANCE that is returned,
+    not raised (LPSolver.solve_batch hands one back per failed form); None for OPTIMAL."""
     if status == _lib.OPTIMAL:
-        return
+        return None
     msg = _lib.status_message(status)
     if status in (_lib.UNBOUNDED, _lib.AUX_UNBOUNDED, _lib.NO_DEGENERATE_PIVOT):
-        raise SolutionException(msg)                 # LPSolver.java:105, :149, :193
+        return SolutionException(msg)                 # LPSolver.java:105, :149, :193
     if status == _lib.INFEASIBLE:
-        raise LPException(msg)                       # LPSolver.java:173
+        return LPException(msg)                       # LPSolver.java:173
     if status == _lib.BAD_ARGUMENT:
-        raise ValueError(_lib.last_error() or msg)   # IllegalArgumentException, LPState.java:288
+        return ValueError(_lib.last_error() or msg)   # IllegalArgumentException, LPState.java:288
     if status == _lib.RESTORE_INDEX_FAULT:
-        raise IndexError(msg)                        # ArrayIndexOutOfBoundsException, LPSolver.java:231
+        return IndexError(msg)                        # ArrayIndexOutOfBoundsException, LPSolver.java:231
     if status == _lib.DIVIDE_BY_ZERO:
-        raise ZeroDivisionError(msg)                 # ArithmeticException, LPState.java:139
+        return ZeroDivisionError(msg)                 # ArithmeticException, LPState.java:139
     if status == _lib.PIVOT_LIMIT:
-        raise RuntimeError("pivot limit reached")
-    raise RuntimeError("%s: %s" % (msg, _lib.last_error()))
+        return RuntimeError("pivot limit reached")
+    return RuntimeError("%s: %s" % (msg, _lib.last_error()))
+
+
+def raise_for_status(status):
+    """Raise what the reference would have thrown for a non-OPTIMAL lpx_status."""
+    exc = exception_for_status(status)
+    if exc is not None:
+        raise exc

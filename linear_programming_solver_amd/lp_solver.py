@@ -8,7 +8,7 @@ from decimal import Decimal
 import numpy as np
 
 from . import _lib
-from .errors import raise_for_status
+from .errors import exception_for_status, raise_for_status
 from .java_compat import hashmap_key_order
 from .lp_state import LPState
 
@@ -44,6 +44,8 @@ class LPSolver:
         self.max_pivots = int(max_pivots)
         self.pricing = _lib.PRICING[pricing]
         self.last = None
+        self.last_batch = None            # solve_batch: one SolveInfo per form
+        self.last_batch_in_kernel = 0     # ... and how many of the forms the batch kernel solved
 
     def _arith_options(self):
         return {} if self.fused is None else {"fused": int(self.fused)}
@@ -90,6 +92,54 @@ class LPSolver:
         if rc != _lib.OPTIMAL:
             raise_for_status(rc)
         return Decimal(res.objective_text.decode())
+
+    def solve_batch(self, forms):
+        """LPSolver.solve for many small forms at once (lpx_solve_batch): the forms that need no phase 1 (min b >= 0)
+        are solved together by ONE launch of the batch kernel, the others one by one.  Returns a list with one entry
+        per form: the Decimal solve() would return, or the exception INSTANCE solve() would raise (the reference's
+        class and message) — returned, not raised, so one unbounded form does not hide the others.  self.last_batch
+        holds a SolveInfo per form, self.last_batch_in_kernel how many forms the batch kernel took.  Every form must
+        fit the batch kernel (lpx_batch_lds_bytes); single device only."""
+        from .lp_batch import pack_lps
+        L = _lib.lib()
+        forms = list(forms)
+        infos, answers = [None] * len(forms), [None] * len(forms)
+        # a NAMED form that needs phase 1 substitutes in the key-set order of its own names (restoreInitialLP): solve()
+        packed_idx = []
+        for k, f in enumerate(forms):
+            if f.has_variable_names() and f.n > 0 and self.min_in_b(f.b) != -1 and np.min(f.b) < 0.0:
+                try:
+                    answers[k] = self.solve(f)
+                except Exception as exc:   # what solve() raises is this form's entry
+                    answers[k] = exc
+                infos[k] = self.last
+            else:
+                packed_idx.append(k)
+        in_kernel = C.c_int32(0)
+        if packed_idx:
+            p = pack_lps([(forms[k].A, forms[k].b, forms[k].c) for k in packed_idx])
+            maxi = np.array([1 if forms[k].maximize else 0 for k in packed_idx], dtype=np.int32)
+            opts = _lib.SolveOptions()
+            opts.device = self.device
+            opts.max_pivots = self.max_pivots
+            opts.pricing = self.pricing
+            opts.fused = 0 if self.fused is None else (1 if self.fused else -1)
+            opts.restore_order_len = -1
+            res = (_lib.SolveResult * len(packed_idx))()
+            rc = L.lpx_solve_batch(p["count"], p["m_max"], p["n_max"], p["m"].ctypes.data_as(_lib.ip),
+                                   p["n"].ctypes.data_as(_lib.ip), p["A"].ctypes.data_as(_lib.dp) if p["A"].size else None,
+                                   p["lda"], p["strideA"], p["b"].ctypes.data_as(_lib.dp) if p["b"].size else None,
+                                   p["c"].ctypes.data_as(_lib.dp) if p["c"].size else None, maxi.ctypes.data_as(_lib.ip),
+                                   C.byref(opts), res, C.byref(in_kernel))
+            if rc:
+                raise_for_status(rc)
+            for t, k in enumerate(packed_idx):
+                infos[k] = SolveInfo(res[t], None, None)
+                exc = exception_for_status(res[t].status)
+                answers[k] = Decimal(res[t].objective_text.decode()) if exc is None else exc
+        self.last_batch = infos
+        self.last_batch_in_kernel = int(in_kernel.value)
+        return answers
 
     @staticmethod
     def _key_set_order(form):
