@@ -388,6 +388,13 @@ int lpx_solve_multi(int32_t m, int32_t n, const double* A, int64_t lda, const do
  * — the image A | b | c | v | perm, the saved entering column, the reduction scratch.  64 x 64: 35 856 (four per CU);
  * the largest LP with 200 columns has 98 rows.  Negative m or n: -1. */
 int64_t lpx_batch_lds_bytes(int32_t m, int32_t n);
+/* Host-only: LDS bytes an m x n standard form needs in lpx_batch_solve IF IT TAKES PHASE 1 (minInB finds a negative b).
+ * The workgroup then holds the m x (n + 1) auxiliary LP and, behind it, what restoreInitialLP reads — c0[n], the restore
+ * order int32[n] and the slot of every original variable int32[n]:
+ *   lpx_batch_lds_bytes(m, n + 1) + 16 * ev(n)
+ * A form that needs no phase 1 needs lpx_batch_lds_bytes(m, n) there as everywhere.  64 x 64: 36 896 (still four per
+ * CU); the largest phase-1 form with 200 columns has 96 rows.  Negative m or n: -1. */
+int64_t lpx_batch_solve_lds_bytes(int32_t m, int32_t n);
 
 typedef struct lpx_batch lpx_batch;
 /* new LPState(A, b, c, v, variables, coefficients, m, n), `count` times   LPState.java:88-112
@@ -409,11 +416,31 @@ int lpx_batch_set_pricing(lpx_batch* s, int32_t pricing);
  * lpx_simplex_loop for every LP of the batch, in ONE launch: pivots_done[count], status[count] (LPX_OPTIMAL |
  * LPX_UNBOUNDED | LPX_PIVOT_LIMIT per LP); max_pivots (<0: unlimited) is the budget of EACH LP.  track_slot[count]
  * (or NULL) follows one slot per LP through the pivots as solveAuxLP does for x0 (LPSolver.java:151-155), in and out;
- * -1 = none for that LP.  The states stay on the device: a later call resumes from them. */
+ * -1 = none for that LP.  The states stay on the device: a later call resumes from them.  A handle that lpx_batch_solve
+ * has solved takes no further loop: LPX_BAD_ARGUMENT. */
 int lpx_batch_simplex_loop(lpx_batch* s, int64_t max_pivots, int64_t* pivots_done, int32_t* status, int32_t* track_slot);
 /* Read-back of LP `index` as lpx_state_read (host pointers, any may be NULL; A row-major with leading dimension lda >= n). */
 int lpx_batch_read(lpx_batch* s, int32_t index, double* A, int64_t lda, double* b, double* c, double* v, int32_t* perm);
 int lpx_batch_count(const lpx_batch* s);
+/* Current shape of LP `index`: m and n as created, n + 1 columns after an lpx_batch_solve that ended inside phase 1 (the
+ * LP is then the auxiliary LP, as lpx_solve leaves it in keep_state).  lpx_batch_read follows it. */
+int lpx_batch_shape(const lpx_batch* s, int32_t index, int32_t* m, int32_t* n);
+/* BigDecimal LPSolver.solve(LPStandardForm stForm) for every LP of the handle        LPSolver.java:78-246
+ * ONE launch, one workgroup per LP, phase 1 included: minInB, convertIntoAuxLP, the forced pivot, the loop with x0
+ * tracked, handleInitialization, the degenerate pivot, restoreInitialLP (bug for bug, as lpx_restore_initial_lp) and the
+ * loop of phase 2 all run on the LP in LDS.  The handle must hold the start of LPSolver.solve, else
+ * LPX_BAD_ARGUMENT: created from A, b, c of standard forms with v NULL or all zero and perm NULL (a nonzero v or a perm
+ * is refused), and no loop or solve run on it yet; afterwards it holds the final states
+ * (lpx_batch_shape, lpx_batch_read) and takes no further loop.  maximize[count] (NULL: every LP is a maximisation; for
+ * `min` c is negated on chip and stays negated in the state, the objective is corrected in the result).  max_pivots is
+ * the budget of each LP's whole solve as in lpx_solve_options.  restore_order[count * n_max] with
+ * restore_order_len[count] (NULL: every LP's order has n[k] entries) give the order of restoreInitialLP per LP with
+ * the semantics of lpx_solve_options; restore_order NULL: lpx_java_default_name_order(n[k]).  results[count] is what
+ * lpx_solve fills for each LP; the times are those of the whole call.  Before any device call: an LP that needs phase 1
+ * and whose lpx_batch_solve_lds_bytes exceeds LPX_BATCH_LDS_BYTES, or a bad order entry, give LPX_BAD_ARGUMENT
+ * (lpx_last_error names the LP and its shape).  Returns 0 when the call itself worked. */
+int lpx_batch_solve(lpx_batch* s, const int32_t* maximize, int64_t max_pivots, const int32_t* restore_order,
+                    const int32_t* restore_order_len, lpx_solve_result* results);
 /* BigDecimal LPSolver.solve(LPStandardForm stForm), `count` times        LPSolver.java:78
  * Standard forms laid out as for lpx_batch_create; maximize[count].  results[k] is what lpx_solve fills for LP k alone
  * (status, phase1_used, objective, objective_text, objective_rounded, pivot counts, x0_slot); seconds_total and
@@ -429,6 +456,24 @@ int lpx_solve_batch(int32_t count, int32_t m_max, int32_t n_max, const int32_t* 
                     const double* A, int64_t lda, int64_t strideA, const double* b, const double* c,
                     const int32_t* maximize, const lpx_solve_options* opts, lpx_solve_result* results,
                     int32_t* n_in_batch);
+
+/* Solutions of every LP from ONE read-back of the handle: x_out (may be NULL) double[count * n_max], LP k at k * n_max, a
+ * basic original variable takes b[row], every other is 0; perm_out (may be NULL) int32[count * (n_max + m_max)], LP k's
+ * slot -> variable id at k * (n_max + m_max).  An LP whose current shape is not m x n as created (lpx_batch_shape: the
+ * auxiliary LP of a solve that ended inside phase 1) is left untouched in both. */
+int lpx_batch_solutions(lpx_batch* s, double* x_out, int32_t* perm_out);
+/* lpx_solve_batch with phase 1 inside the batch kernel and with the solutions: create a handle, lpx_batch_solve, destroy.
+ * Every form that fits the kernel takes it — lpx_batch_solve_lds_bytes where the form needs phase 1 — and only a phase-1
+ * form whose auxiliary LP does not fit falls back to lpx_solve; *n_in_batch counts the forms the kernel took.
+ * maximize NULL: every form is a maximisation.  x_out (may be NULL) is double[count * n_max]: LP k's solution at
+ * k * n_max, a basic original variable takes b[row], every other is 0.  perm_out (may be NULL) is
+ * int32[count * (n_max + m_max)]: LP k's final slot -> variable id at k * (n_max + m_max).  Both are written for LP k
+ * only when its final state is m x n, as in lpx_solve.  opts->restore_order applies that one order to every phase-1 form;
+ * opts->keep_state, opts->perm_out and opts->x_out must be NULL.  All argument checks come before the first device call. */
+int lpx_solve_batch_all(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n,
+                        const double* A, int64_t lda, int64_t strideA, const double* b, const double* c,
+                        const int32_t* maximize, const lpx_solve_options* opts, lpx_solve_result* results,
+                        double* x_out, int32_t* perm_out, int32_t* n_in_batch);
 
 /* LPState restoreInitialLP(auxLP, initial, indexOfX0)                   LPSolver.java:200-246
  * In place on the auxiliary-LP handle (m x (n+1), as left by phase 1): drops x0's column, rebuilds c and v by

@@ -159,6 +159,12 @@ SYMBOLS = [
     ("lpx_batch_count", C.c_int, [C.c_void_p]),
     ("lpx_solve_batch", C.c_int, [C.c_int32, C.c_int32, C.c_int32, ip, ip, dp, C.c_int64, C.c_int64, dp, dp, ip,
                                   C.POINTER(SolveOptions), C.POINTER(SolveResult), ip]),
+    ("lpx_batch_solve_lds_bytes", C.c_int64, [C.c_int32, C.c_int32]),
+    ("lpx_batch_shape", C.c_int, [C.c_void_p, C.c_int32, ip, ip]),
+    ("lpx_batch_solutions", C.c_int, [C.c_void_p, dp, ip]),
+    ("lpx_batch_solve", C.c_int, [C.c_void_p, ip, C.c_int64, ip, ip, C.POINTER(SolveResult)]),
+    ("lpx_solve_batch_all", C.c_int, [C.c_int32, C.c_int32, C.c_int32, ip, ip, dp, C.c_int64, C.c_int64, dp, dp, ip,
+                                      C.POINTER(SolveOptions), C.POINTER(SolveResult), dp, ip, ip]),
 ]
 
 _lib = None

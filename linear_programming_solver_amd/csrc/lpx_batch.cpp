@@ -29,12 +29,37 @@ struct lpx_batch {
   double* d_image = nullptr;
   int64_t *d_offset = nullptr, *d_pivots = nullptr;
   int32_t *d_m = nullptr, *d_n = nullptr, *d_status = nullptr, *d_track = nullptr;
+  // lpx_batch_solve
+  std::vector<int32_t> n_cur;       // columns of LP k now: n[k], or n[k] + 1 after a solve that ended inside phase 1
+  std::vector<int32_t> need_p1;     // minInB of the b given at creation finds a negative entry: the image has room for n + 1 columns
+  bool custom_start = false;        // created with a nonzero v or with perm: not the start of LPSolver.solve
+  int state = 0;                    // 0: as created, 1: a loop has run, 2: solved
+  int32_t solve_threads = 64;       // workgroup size of k_batch_solve: by the auxiliary shape where phase 1 is due
+  // inputs and outputs of k_batch_solve, allocated with the handle: flags, orders, 4 int32 / 2 int64 / 1 double per LP
+  int32_t *d_max = nullptr, *d_p1 = nullptr, *d_order = nullptr, *d_olen = nullptr, *d_si32 = nullptr;
+  int64_t* d_si64 = nullptr;
+  double* d_sv = nullptr;
 };
 
 namespace {
 
 double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// minInB (LPSolver.java:375-386) finds an entry below 0: the form needs the auxiliary LP (:119)
+bool needs_phase1(const double* b, int32_t m) {
+  double mn = 1e50;
+  int idx = -1;
+  for (int i = 0; i < m; i++)
+    if (mn > b[i]) { mn = b[i]; idx = i; }
+  return !(idx == -1 || b[idx] >= 0.0);
+}
+
+int64_t solve_lds_bytes_of(int64_t m, int64_t n) {
+  if (m < 0 || n < 0) return -1;
+  if ((double)m * (double)((n + 1) | 1) > 1e12) return INT64_MAX;
+  return lpxk::batch_solve_layout(m, n).lds_bytes;
 }
 
 int64_t lds_bytes_of(int64_t m, int64_t n) {
@@ -98,6 +123,13 @@ void free_batch(lpx_batch* B) {
     (void)hipFree(B->d_n);
     (void)hipFree(B->d_status);
     (void)hipFree(B->d_track);
+    (void)hipFree(B->d_max);
+    (void)hipFree(B->d_p1);
+    (void)hipFree(B->d_order);
+    (void)hipFree(B->d_olen);
+    (void)hipFree(B->d_si32);
+    (void)hipFree(B->d_si64);
+    (void)hipFree(B->d_sv);
     if (B->stream) (void)hipStreamDestroy(B->stream);
   }
   delete B;
@@ -121,20 +153,28 @@ int create_checked(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m
   B->m.resize(count);
   B->n.resize(count);
   B->offset.resize((size_t)count + 1);
+  B->need_p1.resize(count);
+  B->custom_start = perm != nullptr;
+  for (int32_t k = 0; v && k < count; k++) B->custom_start |= !(v[k] == 0.0);
   int64_t total = 0, lds = 0;
-  int threads = 64;
+  int threads = 64, solve_threads = 64;
   for (int32_t k = 0; k < count; k++) {
     B->m[k] = m ? m[k] : m_max;
     B->n[k] = n ? n[k] : n_max;
     const lpxk::BatchLayout L = lpxk::batch_layout(B->m[k], B->n[k]);
+    B->need_p1[k] = B->m[k] > 0 && needs_phase1(b + (int64_t)k * m_max, B->m[k]);
     B->offset[k] = total;
-    total += L.image;
+    // a form that needs phase 1 may come back from lpx_batch_solve as its m x (n + 1) auxiliary LP
+    total += B->need_p1[k] ? std::max(L.image, lpxk::batch_layout(B->m[k], B->n[k] + 1).image) : L.image;
     lds = std::max(lds, L.lds_bytes);
     threads = std::max(threads, threads_of(B->m[k], B->n[k]));
+    solve_threads = std::max(solve_threads, threads_of(B->m[k], B->n[k] + (B->need_p1[k] ? 1 : 0)));
   }
+  B->n_cur = B->n;
   B->offset[count] = total;
   B->lds_bytes = (int32_t)lds;
   B->threads = threads;
+  B->solve_threads = solve_threads;
   std::vector<double> img((size_t)total, 0.0);
   for (int32_t k = 0; k < count; k++) {
     const int32_t mk = B->m[k], nk = B->n[k];
@@ -158,11 +198,19 @@ int create_checked(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m
   HIP_TRY(hipMalloc((void**)&B->d_n, cnt * sizeof(int32_t)));
   HIP_TRY(hipMalloc((void**)&B->d_status, cnt * sizeof(int32_t)));
   HIP_TRY(hipMalloc((void**)&B->d_track, cnt * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_max, cnt * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_p1, cnt * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_order, cnt * (size_t)std::max(n_max, 1) * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_olen, cnt * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_si32, 4 * cnt * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_si64, 2 * cnt * sizeof(int64_t)));
+  HIP_TRY(hipMalloc((void**)&B->d_sv, cnt * sizeof(double)));
   if (total > 0) HIP_TRY(hipMemcpyAsync(B->d_image, img.data(), (size_t)total * sizeof(double), hipMemcpyHostToDevice, B->stream));
   if (count > 0) {
     HIP_TRY(hipMemcpyAsync(B->d_offset, B->offset.data(), (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, B->stream));
     HIP_TRY(hipMemcpyAsync(B->d_m, B->m.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
     HIP_TRY(hipMemcpyAsync(B->d_n, B->n.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+    HIP_TRY(hipMemcpyAsync(B->d_p1, B->need_p1.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
   }
   HIP_TRY(hipStreamSynchronize(B->stream));   // img goes out of scope
   guard.B = nullptr;
@@ -172,13 +220,51 @@ int create_checked(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m
 
 // LPX_BATCH_THREADS (debugging aid of scripts/bench_batch.py, read at every loop call): workgroup size instead of the
 // by-size choice, rounded down to a multiple of 64 inside 64..1024
-int threads_in_effect(const lpx_batch* B) {
+int threads_in_effect(const lpx_batch* B, bool solve = false) {
   const char* e = getenv("LPX_BATCH_THREADS");
   if (e && *e) {
     const int t = atoi(e);
     if (t > 0) return std::max(64, std::min(1024, t / 64 * 64));
   }
-  return B->threads;
+  return solve ? B->solve_threads : B->threads;
+}
+
+// dynamic LDS of the k_batch_solve launch: per LP the auxiliary layout where phase 1 is due, else the plain one
+int64_t solve_launch_lds(const lpx_batch* B) {
+  int64_t lds = lpxk::kBatchScratchBytes;
+  for (int32_t k = 0; k < B->count; k++)
+    lds = std::max(lds, B->need_p1[k] ? solve_lds_bytes_of(B->m[k], B->n[k]) : lds_bytes_of(B->m[k], B->n[k]));
+  return lds;
+}
+
+// one restore order of `len` entries (< 0: n) against an LP with n columns
+int check_order(const char* who, int32_t k, int32_t m, int32_t n, const int32_t* order, int32_t len) {
+  char msg[200];
+  if (len < 0) len = n;
+  if (len > n) {
+    snprintf(msg, sizeof msg, "%s: restore order of LP %d (%d x %d) has %d entries", who, k, m, n, len);
+    return fail(LPX_BAD_ARGUMENT, msg);
+  }
+  for (int32_t t = 0; t < len; t++)
+    if (order[t] < 0 || order[t] >= n) {
+      snprintf(msg, sizeof msg, "%s: restore order of LP %d (%d x %d) names variable %d at entry %d", who, k, m, n, order[t], t);
+      return fail(LPX_BAD_ARGUMENT, msg);
+    }
+  return 0;
+}
+
+int too_large_for_phase1(const char* who, int32_t k, int32_t m, int32_t n) {
+  char msg[240];
+  snprintf(msg, sizeof msg, "%s: LP %d of shape %d x %d needs phase 1 and with it %lld bytes of LDS, a workgroup has %d", who, k,
+           m, n, (long long)solve_lds_bytes_of(m, n), LPX_BATCH_LDS_BYTES);
+  return fail(LPX_BAD_ARGUMENT, msg);
+}
+
+void fill_objective(lpx_solve_result& r, double v, bool maximize) {
+  if (!maximize) v = -v;                                                            // LPSolver.java:90
+  r.objective = v;
+  lpx_internal::round6_text(v, r.objective_text, sizeof r.objective_text);         // :113
+  r.objective_rounded = strtod(r.objective_text, nullptr);
 }
 
 }  // namespace
@@ -186,6 +272,12 @@ int threads_in_effect(const lpx_batch* B) {
 extern "C" int64_t lpx_batch_lds_bytes(int32_t m, int32_t n) {
   const int64_t r = lds_bytes_of(m, n);
   if (r < 0) fail(LPX_BAD_ARGUMENT, "lpx_batch_lds_bytes: negative dimension");
+  return r;
+}
+
+extern "C" int64_t lpx_batch_solve_lds_bytes(int32_t m, int32_t n) {
+  const int64_t r = solve_lds_bytes_of(m, n);
+  if (r < 0) fail(LPX_BAD_ARGUMENT, "lpx_batch_solve_lds_bytes: negative dimension");
   return r;
 }
 
@@ -226,6 +318,7 @@ extern "C" int lpx_batch_simplex_loop(lpx_batch* B, int64_t max_pivots, int64_t*
                                       int32_t* track_slot) {
   if (!B) return fail(LPX_BAD_ARGUMENT, "lpx_batch_simplex_loop: NULL handle");
   if (B->count > 0 && (!pivots_done || !status)) return fail(LPX_BAD_ARGUMENT, "lpx_batch_simplex_loop: NULL output array");
+  if (B->state == 2) return fail(LPX_BAD_ARGUMENT, "lpx_batch_simplex_loop: the batch has been solved (lpx_batch_solve)");
   if (B->count == 0) return 0;
   if (track_slot)
     for (int32_t k = 0; k < B->count; k++)
@@ -234,6 +327,7 @@ extern "C" int lpx_batch_simplex_loop(lpx_batch* B, int64_t max_pivots, int64_t*
                                           std::to_string(k) + " is outside its n + m slots");
   DeviceRestore keep_device;
   HIP_TRY(hipSetDevice(B->device));
+  B->state = 1;
   const size_t cnt = (size_t)B->count;
   if (track_slot) HIP_TRY(hipMemcpyAsync(B->d_track, track_slot, cnt * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
   else HIP_TRY(hipMemsetAsync(B->d_track, 0xff, cnt * sizeof(int32_t), B->stream));   // -1: nothing tracked
@@ -262,7 +356,7 @@ extern "C" int lpx_batch_simplex_loop(lpx_batch* B, int64_t max_pivots, int64_t*
 extern "C" int lpx_batch_read(lpx_batch* B, int32_t index, double* A, int64_t lda, double* b, double* c, double* v,
                               int32_t* perm) {
   if (!B || index < 0 || index >= B->count) return fail(LPX_BAD_ARGUMENT, "lpx_batch_read: bad handle or index");
-  const int32_t mk = B->m[index], nk = B->n[index];
+  const int32_t mk = B->m[index], nk = B->n_cur[index];
   if (A && lda < nk) return fail(LPX_BAD_ARGUMENT, "lpx_batch_read: lda < n");
   const lpxk::BatchLayout L = lpxk::batch_layout(mk, nk);
   std::vector<double> img((size_t)L.image);
@@ -276,6 +370,151 @@ extern "C" int lpx_batch_read(lpx_batch* B, int32_t index, double* A, int64_t ld
   if (c && nk > 0) memcpy(c, img.data() + L.c, (size_t)nk * sizeof(double));
   if (v) *v = img[L.v];
   if (perm && nk + mk > 0) memcpy(perm, img.data() + L.perm, ((size_t)nk + mk) * sizeof(int32_t));
+  return 0;
+}
+
+extern "C" int lpx_batch_shape(const lpx_batch* B, int32_t index, int32_t* m, int32_t* n) {
+  if (!B || index < 0 || index >= B->count) return fail(LPX_BAD_ARGUMENT, "lpx_batch_shape: bad handle or index");
+  if (m) *m = B->m[index];
+  if (n) *n = B->n_cur[index];
+  return 0;
+}
+
+// LPSolver.solve (LPSolver.java:78) for every LP of the handle in ONE launch of k_batch_solve: phase 1 included.
+extern "C" int lpx_batch_solve(lpx_batch* B, const int32_t* maximize, int64_t max_pivots, const int32_t* restore_order,
+                               const int32_t* restore_order_len, lpx_solve_result* results) {
+  if (!B) return fail(LPX_BAD_ARGUMENT, "lpx_batch_solve: NULL handle");
+  if (B->state != 0) return fail(LPX_BAD_ARGUMENT, "lpx_batch_solve: a loop or a solve has already run on this handle");
+  if (B->custom_start) return fail(LPX_BAD_ARGUMENT, "lpx_batch_solve: the handle was created with a nonzero v or with perm, not from standard forms");
+  const int32_t count = B->count;
+  if (count > 0 && !results) return fail(LPX_BAD_ARGUMENT, "lpx_batch_solve: results is NULL");
+  if (count == 0) return 0;
+  const double t_start = now_s();
+  const int64_t pitch = std::max(B->n_max, 1);
+  std::vector<int32_t> order((size_t)count * pitch, 0), olen(count, 0);
+  for (int32_t k = 0; k < count; k++) {
+    if (!B->need_p1[k]) continue;
+    const int32_t mk = B->m[k], nk = B->n[k];
+    if (solve_lds_bytes_of(mk, nk) > LPX_BATCH_LDS_BYTES) return too_large_for_phase1("lpx_batch_solve", k, mk, nk);
+    if (restore_order) {
+      const int32_t* ok = restore_order + (int64_t)k * B->n_max;
+      const int32_t len = restore_order_len ? restore_order_len[k] : -1;
+      if (int rc = check_order("lpx_batch_solve", k, mk, nk, ok, len)) return rc;
+      olen[k] = len < 0 ? nk : len;
+      std::copy(ok, ok + olen[k], order.begin() + (int64_t)k * pitch);
+    } else {
+      olen[k] = nk;
+      if (nk > 0) lpx_java_default_name_order(nk, order.data() + (int64_t)k * pitch);
+    }
+  }
+  for (int32_t k = 0; k < count; k++) {
+    memset(&results[k], 0, sizeof results[k]);
+    results[k].x0_slot = -1;
+    results[k].status = LPX_BAD_ARGUMENT;
+  }
+  DeviceRestore keep_device;
+  HIP_TRY(hipSetDevice(B->device));
+  const size_t cnt = (size_t)count;
+  if (maximize) HIP_TRY(hipMemcpyAsync(B->d_max, maximize, cnt * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+  HIP_TRY(hipMemcpyAsync(B->d_order, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+  HIP_TRY(hipMemcpyAsync(B->d_olen, olen.data(), cnt * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+  lpxk::BatchSolveArgs a{};
+  a.count = count;
+  a.m = B->d_m;
+  a.n = B->d_n;
+  a.offset = B->d_offset;
+  a.image = B->d_image;
+  a.maximize = maximize ? B->d_max : nullptr;
+  a.phase1 = B->d_p1;
+  a.order = B->d_order;
+  a.order_len = B->d_olen;
+  a.order_pitch = pitch;
+  a.status = B->d_si32;
+  a.phase1_used = a.status + cnt;
+  a.x0_slot = a.status + 2 * cnt;
+  a.n_final = a.status + 3 * cnt;
+  a.pivots1 = B->d_si64;
+  a.pivots2 = a.pivots1 + cnt;
+  a.v = B->d_sv;
+  a.max_pivots = max_pivots < 0 ? -1 : max_pivots;
+  a.dantzig = B->pricing == 1;
+  a.fused = B->fused;
+  a.lds_bytes = (int32_t)solve_launch_lds(B);
+  a.threads = threads_in_effect(B, true);
+  B->state = 2;
+  std::vector<int32_t> h_i32(4 * cnt);
+  std::vector<int64_t> h_i64(2 * cnt);
+  std::vector<double> h_v(cnt);
+  const double t0 = now_s();
+  HIP_TRY(lpxk::launch_batch_solve(a, B->stream));
+  HIP_TRY(hipStreamSynchronize(B->stream));
+  const double t_pivots = now_s() - t0;
+  HIP_TRY(hipMemcpyAsync(h_i32.data(), B->d_si32, h_i32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipMemcpyAsync(h_i64.data(), B->d_si64, h_i64.size() * sizeof(int64_t), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipMemcpyAsync(h_v.data(), B->d_sv, h_v.size() * sizeof(double), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipStreamSynchronize(B->stream));
+  bool device_error = false;
+  for (int32_t k = 0; k < count; k++) {
+    lpx_solve_result& r = results[k];
+    r.status = h_i32[k];
+    r.phase1_used = h_i32[cnt + k];
+    r.x0_slot = h_i32[2 * cnt + k];
+    B->n_cur[k] = h_i32[3 * cnt + k];
+    r.pivots_phase1 = h_i64[k];
+    r.pivots_phase2 = h_i64[cnt + k];
+    fill_objective(r, h_v[k], !maximize || maximize[k] != 0);
+    device_error |= r.status == LPX_DEVICE_ERROR;
+  }
+  const double t_total = now_s() - t_start;
+  for (int32_t k = 0; k < count; k++) {
+    results[k].seconds_total = t_total;
+    results[k].seconds_pivots = t_pivots;
+  }
+  if (device_error) return fail(LPX_DEVICE_ERROR, "lpx_batch_solve: the kernel and the host disagree about an LP's layout");
+  return 0;
+}
+
+// x and perm of every LP from ONE copy of the images
+extern "C" int lpx_batch_solutions(lpx_batch* B, double* x_out, int32_t* perm_out) {
+  if (!B) return fail(LPX_BAD_ARGUMENT, "lpx_batch_solutions: NULL handle");
+  if ((!x_out && !perm_out) || B->count == 0) return 0;
+  DeviceRestore keep_device;
+  HIP_TRY(hipSetDevice(B->device));
+  std::vector<double> img((size_t)B->offset[B->count]);
+  if (!img.empty()) {
+    HIP_TRY(hipMemcpyAsync(img.data(), B->d_image, img.size() * sizeof(double), hipMemcpyDeviceToHost, B->stream));
+    HIP_TRY(hipStreamSynchronize(B->stream));
+  }
+  const int64_t pw = (int64_t)B->n_max + B->m_max;
+  for (int32_t k = 0; k < B->count; k++) {
+    const int32_t mk = B->m[k], nk = B->n[k];
+    if (B->n_cur[k] != nk) continue;   // the auxiliary LP of a solve that ended inside phase 1: not the caller's variables
+    const lpxk::BatchLayout L = lpxk::batch_layout(mk, nk);
+    const double* g = img.data() + B->offset[k];
+    const int32_t* fp = (const int32_t*)(g + L.perm);
+    if (perm_out && nk + mk > 0) memcpy(perm_out + k * pw, fp, ((size_t)nk + mk) * sizeof(int32_t));
+    if (x_out) {
+      double* x = x_out + (int64_t)k * B->n_max;
+      for (int32_t j = 0; j < nk; j++) x[j] = 0.0;
+      for (int32_t i = 0; i < mk; i++) {
+        const int32_t id = fp[(size_t)nk + i];
+        if (id >= 0 && id < nk) x[id] = g[L.b + i];
+      }
+    }
+  }
+  return 0;
+}
+
+// What the launch of lpx_batch_solve on this handle looks like (scripts/bench_batch.py): not part of include/lpx.h
+extern "C" int lpxi_batch_solve_launch_info(lpx_batch* B, int32_t* threads, int32_t* lds_bytes, int32_t* blocks_per_cu) {
+  if (!B) return fail(LPX_BAD_ARGUMENT, "lpxi_batch_solve_launch_info: NULL handle");
+  DeviceRestore keep_device;
+  HIP_TRY(hipSetDevice(B->device));
+  const int t = threads_in_effect(B, true);
+  const int lds = (int)std::min<int64_t>(solve_launch_lds(B), INT32_MAX);
+  if (threads) *threads = t;
+  if (lds_bytes) *lds_bytes = lds;
+  if (blocks_per_cu) *blocks_per_cu = lpxk::batch_solve_blocks_per_cu(t, lds);
   return 0;
 }
 
@@ -373,6 +612,109 @@ extern "C" int lpx_solve_batch(int32_t count, int32_t m_max, int32_t n_max, cons
     const int rc = lpx_solve(m ? m[k] : m_max, n ? n[k] : n_max, A ? A + (int64_t)k * strideA : nullptr, lda,
                              b ? b + (int64_t)k * m_max : nullptr, c ? c + (int64_t)k * n_max : nullptr, maximize[k], &oa,
                              &results[k]);
+    if (rc == LPX_DEVICE_ERROR || rc == LPX_BAD_ARGUMENT) return rc;
+    t_pivots += results[k].seconds_pivots;
+  }
+  const double t_total = now_s() - t_start;
+  for (int32_t k = 0; k < count; k++) {
+    results[k].seconds_total = t_total;
+    results[k].seconds_pivots = t_pivots;
+  }
+  return 0;
+}
+
+// LPSolver.solve for `count` standard forms with phase 1 INSIDE the batch kernel: every form that fits k_batch_solve
+// (lpx_batch_solve_lds_bytes where minInB finds a negative b, lpx_batch_lds_bytes otherwise) goes through one handle and
+// one launch; a phase-1 form whose auxiliary LP does not fit takes lpx_solve, as in lpx_solve_batch.
+extern "C" int lpx_solve_batch_all(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n,
+                                   const double* A, int64_t lda, int64_t strideA, const double* b, const double* c,
+                                   const int32_t* maximize, const lpx_solve_options* opts, lpx_solve_result* results,
+                                   double* x_out, int32_t* perm_out, int32_t* n_in_batch) {
+  const char* who = "lpx_solve_batch_all";
+  if (n_in_batch) *n_in_batch = 0;
+  if (int rc = check_shapes(who, count, m_max, n_max, m, n)) return rc;
+  if (int rc = check_arrays(who, count, m_max, n_max, m, n, A, lda, strideA, b, c)) return rc;
+  if (count > 0 && !results) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": results is NULL");
+  lpx_solve_options o{};
+  o.max_pivots = -1;
+  if (opts) o = *opts;
+  if (o.keep_state || o.perm_out || o.x_out)
+    return fail(LPX_BAD_ARGUMENT, std::string(who) + ": opts->keep_state, opts->perm_out and opts->x_out must be NULL");
+  if (o.device < 0 || (o.pricing != 0 && o.pricing != 1)) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": bad device or pricing");
+  std::vector<int32_t> in_batch, alone;
+  for (int32_t k = 0; k < count; k++) {
+    const int32_t mk = m ? m[k] : m_max, nk = n ? n[k] : n_max;
+    const bool p1 = mk > 0 && needs_phase1(b + (int64_t)k * m_max, mk);
+    if (p1 && o.restore_order)
+      if (int rc = check_order(who, k, mk, nk, o.restore_order, o.restore_order_len)) return rc;
+    (p1 && solve_lds_bytes_of(mk, nk) > LPX_BATCH_LDS_BYTES ? alone : in_batch).push_back(k);
+  }
+  const double t_start = now_s();
+  for (int32_t k = 0; k < count; k++) {
+    memset(&results[k], 0, sizeof results[k]);
+    results[k].x0_slot = -1;
+    results[k].status = LPX_BAD_ARGUMENT;
+  }
+  double t_pivots = 0.0;
+  const int32_t nb = (int32_t)in_batch.size();
+  const int64_t pw = (int64_t)n_max + m_max;
+  if (nb > 0) {
+    std::vector<int32_t> bm(nb), bn(nb), bmax(nb), border, blen;
+    std::vector<double> bb((size_t)nb * m_max, 0.0), bc((size_t)nb * n_max, 0.0), bA;
+    const int64_t ldp = std::max(n_max, 1), strideP = (int64_t)m_max * ldp;
+    bA.assign((size_t)nb * strideP, 0.0);
+    if (o.restore_order) {
+      border.assign((size_t)nb * n_max, 0);
+      blen.assign(nb, 0);
+    }
+    for (int32_t t = 0; t < nb; t++) {
+      const int32_t k = in_batch[t];
+      bm[t] = m ? m[k] : m_max;
+      bn[t] = n ? n[k] : n_max;
+      bmax[t] = !maximize || maximize[k] != 0;
+      for (int32_t i = 0; i < bm[t]; i++)
+        if (bn[t] > 0) memcpy(&bA[(size_t)t * strideP + (size_t)i * ldp], A + (int64_t)k * strideA + (int64_t)i * lda, (size_t)bn[t] * sizeof(double));
+      for (int32_t i = 0; i < bm[t]; i++) bb[(size_t)t * m_max + i] = b[(int64_t)k * m_max + i];
+      for (int32_t j = 0; j < bn[t]; j++) bc[(size_t)t * n_max + j] = c[(int64_t)k * n_max + j];
+      if (o.restore_order) {   // the one order for every phase-1 form, as lpx_solve_batch hands it to lpx_solve
+        blen[t] = std::min(o.restore_order_len < 0 ? bn[t] : o.restore_order_len, bn[t]);
+        std::copy(o.restore_order, o.restore_order + blen[t], border.begin() + (size_t)t * n_max);
+      }
+    }
+    DeviceRestore keep_device;
+    BatchGuard guard;
+    if (int rc = create_checked(nb, m_max, n_max, bm.data(), bn.data(), bA.data(), ldp, strideP, bb.data(), bc.data(), nullptr,
+                                nullptr, o.device, &guard.B))
+      return rc;
+    lpx_batch* B = guard.B;
+    B->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
+    B->pricing = o.pricing;
+    std::vector<lpx_solve_result> res(nb);
+    if (int rc = lpx_batch_solve(B, bmax.data(), o.max_pivots, o.restore_order ? border.data() : nullptr,
+                                 o.restore_order ? blen.data() : nullptr, res.data()))
+      return rc;
+    t_pivots = res[0].seconds_pivots;
+    std::vector<double> bx;
+    std::vector<int32_t> bp;
+    if (x_out) bx.assign((size_t)nb * n_max, 0.0);
+    if (perm_out) bp.assign((size_t)nb * pw, 0);
+    if (int rc = lpx_batch_solutions(B, x_out ? bx.data() : nullptr, perm_out ? bp.data() : nullptr)) return rc;
+    for (int32_t t = 0; t < nb; t++) {
+      const int32_t k = in_batch[t];
+      results[k] = res[t];
+      if (B->n_cur[t] != bn[t]) continue;   // as lpx_solve: only an m x n state is the caller's
+      if (perm_out && bn[t] + bm[t] > 0) memcpy(perm_out + k * pw, bp.data() + t * pw, ((size_t)bn[t] + bm[t]) * sizeof(int32_t));
+      if (x_out && bn[t] > 0) memcpy(x_out + (int64_t)k * n_max, bx.data() + (size_t)t * n_max, (size_t)bn[t] * sizeof(double));
+    }
+  }
+  if (n_in_batch) *n_in_batch = nb;
+  for (int32_t k : alone) {
+    lpx_solve_options oa = o;
+    oa.x_out = x_out ? x_out + (int64_t)k * n_max : nullptr;
+    oa.perm_out = perm_out ? perm_out + k * pw : nullptr;
+    const int rc = lpx_solve(m ? m[k] : m_max, n ? n[k] : n_max, A ? A + (int64_t)k * strideA : nullptr, lda,
+                             b ? b + (int64_t)k * m_max : nullptr, c ? c + (int64_t)k * n_max : nullptr,
+                             !maximize || maximize[k] != 0, &oa, &results[k]);
     if (rc == LPX_DEVICE_ERROR || rc == LPX_BAD_ARGUMENT) return rc;
     t_pivots += results[k].seconds_pivots;
   }

@@ -38,6 +38,125 @@ __device__ __forceinline__ RatioRow batch_reduce(RatioRow x, RatioRow* sh, int l
   return r;
 }
 
+// One LP in LDS as the loop and the pivot see it: pointers into the workgroup's LDS, the row pitch, the CURRENT number of
+// columns (k_batch_solve changes it between the phases) and the thread's place in the workgroup.
+struct BatchLp {
+  double *A, *b, *c, *vp, *col;
+  int32_t* perm;
+  RatioRow *sh_e, *sh_l;   // 16 entries each: the per-wave partials of the entering and of the leaving reduction
+  int ld, m, n;
+  int tid, T, lane, wave, nw;
+  int dantzig;
+};
+
+// getEntering() over the whole of c (LPState.java:274-285): one barrier
+__device__ __forceinline__ RatioRow batch_entering(const BatchLp& S) {
+  RatioRow ent = rr_none();
+  for (int j = S.tid; j < S.n; j += S.T) batch_consider(ent, S.c[j], j, S.dantzig);
+  return batch_reduce(ent, S.sh_e, S.lane, S.wave, S.nw);
+}
+
+// col[i] = A[i][e] for a pivot that no ratio test precedes (the forced and the degenerate pivot of phase 1): one barrier
+__device__ __forceinline__ void batch_save_column(const BatchLp& S, int e) {
+  for (int i = S.tid; i < S.m; i += S.T) S.col[i] = S.A[i * S.ld + e];
+  __syncthreads();
+}
+
+// pivot(e, l), LPState.java:133-181, on an LP whose column e stands in col[] (visible to every thread).  Returns the
+// entering choice of the NEXT iteration, folded from the new c on the way; ends behind barrier B2.
+__device__ __forceinline__ RatioRow batch_pivot(const BatchLp& S, int e, int l) {
+  double* const A = S.A;
+  double* const b = S.b;
+  double* const c = S.c;
+  const double* const col = S.col;
+  const int ld = S.ld, m = S.m, n = S.n, tid = S.tid, T = S.T, lane = S.lane, wave = S.wave, nw = S.nw;
+  const int dantzig = S.dantzig;
+  const int nq = (n + 63) >> 6;
+  const int groups = nq > 0 && nw > nq ? nw / nq : 1;
+  // piv, pc and b[l] are read here by every thread; their new values are stored behind barrier B1 only
+  const double piv = col[l], pc = c[e];
+  const double bl = __ddiv_rn(b[l], piv);                                           // :146
+  double* const prow = A + l * ld;
+  double ce_new = 0.0;
+  RatioRow ent = rr_none();
+  for (int j = tid; j < n; j += T) {
+    if (j == e) {
+      prow[j] = __ddiv_rn(1.0, piv);                                                // :139
+      ce_new = -__ddiv_rn(pc, piv);                                                 // :172
+      batch_consider(ent, ce_new, j, dantzig);
+    } else {
+      const double pr = __ddiv_rn(prow[j], piv);                                    // :144
+      const double cn = submul(c[j], pc, pr);                                       // :177
+      prow[j] = pr;
+      c[j] = cn;
+      batch_consider(ent, cn, j, dantzig);
+    }
+  }
+  ent = batch_reduce(ent, S.sh_e, lane, wave, nw);                                  // barrier B1
+  if (tid == e % T) c[e] = ce_new;
+  if (tid == 0) {
+    b[l] = bl;
+    *S.vp = addmul(*S.vp, bl, pc);                                                  // :171
+    const int32_t pe = S.perm[e];                                                   // exchangeIndexes :311-320
+    S.perm[e] = S.perm[n + l];
+    S.perm[n + l] = pe;
+  }
+  for (int i = tid; i < m; i += T) {
+    if (i == l) continue;
+    const double ce = col[i];
+    A[i * ld + e] = -__ddiv_rn(ce, piv);                                            // :157
+    b[i] = submul(b[i], ce, bl);                                                    // :164
+  }
+  for (int u = wave; u < nq * groups; u += nw) {
+    const int j = ((u % nq) << 6) + lane;
+    if (j >= n || j == e) continue;
+    const double pr = prow[j];
+    double* const Aj = A + j;
+    const int g = groups;
+    int i = u / nq;
+    for (; i + 3 * g < m; i += 4 * g) {                                             // :162, four rows in flight
+      const int i0 = i, i1 = i + g, i2 = i + 2 * g, i3 = i + 3 * g;
+      const double c0 = col[i0], c1 = col[i1], c2 = col[i2], c3 = col[i3];
+      const double x0 = submul(Aj[i0 * ld], c0, pr), x1 = submul(Aj[i1 * ld], c1, pr);
+      const double x2 = submul(Aj[i2 * ld], c2, pr), x3 = submul(Aj[i3 * ld], c3, pr);
+      if (i0 != l) Aj[i0 * ld] = x0;
+      if (i1 != l) Aj[i1 * ld] = x1;
+      if (i2 != l) Aj[i2 * ld] = x2;
+      if (i3 != l) Aj[i3 * ld] = x3;
+    }
+    for (; i < m; i += g)
+      if (i != l) Aj[i * ld] = submul(Aj[i * ld], col[i], pr);
+  }
+  __syncthreads();                                                                  // barrier B2
+  return ent;
+}
+
+// The loop of LPSolver.simplex (LPSolver.java:101-107; solveAuxLP :142-157 with `track`) from the entering choice `ent`.
+// Returns LPX_OPTIMAL, LPX_UNBOUNDED or LPX_PIVOT_LIMIT; `pivots` counts from the caller's value, `track` < 0 follows nothing.
+__device__ __forceinline__ int batch_loop(const BatchLp& S, RatioRow ent, int64_t max_pivots, int64_t& pivots, int& track) {
+  for (;;) {
+    const int e = ent.row == INT_MAX ? -1 : ent.row;                                // :101
+    if (e < 0) return 0 /* LPX_OPTIMAL */;
+    RatioRow best = rr_none();                                                      // getLeaving, LPState.java:287-305
+    for (int i = S.tid; i < S.m; i += S.T) {
+      const double aie = S.A[i * S.ld + e];
+      S.col[i] = aie;
+      const double r = ratio_of(aie, S.b[i]);
+      if (r < kInf) best = rr_min(best, RatioRow{r, i, 0});
+    }
+    best = batch_reduce(best, S.sh_l, S.lane, S.wave, S.nw);                        // barrier L
+    if (!(best.ratio < kInf)) return 1 /* LPX_UNBOUNDED */;                         // :103-106
+    if (max_pivots >= 0 && pivots >= max_pivots) return 9 /* LPX_PIVOT_LIMIT */;
+    const int l = best.row;
+    if (track >= 0) {                                                               // LPSolver.java:151-155
+      if (e == track) track = l + S.n;
+      else if (l + S.n == track) track = e;
+    }
+    ent = batch_pivot(S, e, l);
+    pivots++;
+  }
+}
+
 template <int kThreads>
 __global__ __launch_bounds__(kThreads) void k_batch_simplex(const BatchArgs a) {
   extern __shared__ __attribute__((aligned(16))) double batch_lds[];
@@ -54,108 +173,249 @@ __global__ __launch_bounds__(kThreads) void k_batch_simplex(const BatchArgs a) {
   const int nvec = (int)(L.image >> 1);
   for (int q = tid; q < nvec; q += T) ((d2*)batch_lds)[q] = ((const d2*)image)[q];
 
-  const int ld = (int)L.ld;
-  double* const A = batch_lds;
-  double* const b = batch_lds + L.b;
-  double* const c = batch_lds + L.c;
-  double* const vp = batch_lds + L.v;
-  int32_t* const perm = (int32_t*)(batch_lds + L.perm);
-  double* const col = batch_lds + L.col;
-  RatioRow* const sh_e = (RatioRow*)(col + ((m + 1) & ~1));
-  RatioRow* const sh_l = sh_e + 16;
-  const int dantzig = a.dantzig;
-  const int nq = (n + 63) >> 6;
-  const int groups = nq > 0 && nw > nq ? nw / nq : 1;
+  BatchLp S;
+  S.A = batch_lds;
+  S.b = batch_lds + L.b;
+  S.c = batch_lds + L.c;
+  S.vp = batch_lds + L.v;
+  S.perm = (int32_t*)(batch_lds + L.perm);
+  S.col = batch_lds + L.col;
+  S.sh_e = (RatioRow*)(S.col + ((m + 1) & ~1));
+  S.sh_l = S.sh_e + 16;
+  S.ld = (int)L.ld; S.m = m; S.n = n;
+  S.tid = tid; S.T = T; S.lane = lane; S.wave = wave; S.nw = nw;
+  S.dantzig = a.dantzig;
   __syncthreads();
 
   int64_t pivots = 0;
   int track = a.track[k];
-  int status;
-  RatioRow ent = rr_none();
-  for (int j = tid; j < n; j += T) batch_consider(ent, c[j], j, dantzig);
-  ent = batch_reduce(ent, sh_e, lane, wave, nw);
-  for (;;) {
-    const int e = ent.row == INT_MAX ? -1 : ent.row;                                // :101
-    if (e < 0) { status = 0 /* LPX_OPTIMAL */; break; }
-    RatioRow best = rr_none();                                                      // getLeaving, LPState.java:287-305
-    for (int i = tid; i < m; i += T) {
-      const double aie = A[i * ld + e];
-      col[i] = aie;
-      const double r = ratio_of(aie, b[i]);
-      if (r < kInf) best = rr_min(best, RatioRow{r, i, 0});
-    }
-    best = batch_reduce(best, sh_l, lane, wave, nw);                                // barrier L
-    if (!(best.ratio < kInf)) { status = 1 /* LPX_UNBOUNDED */; break; }            // :103-106
-    if (a.max_pivots >= 0 && pivots >= a.max_pivots) { status = 9 /* LPX_PIVOT_LIMIT */; break; }
-    const int l = best.row;
-    if (track >= 0) {                                                               // LPSolver.java:151-155
-      if (e == track) track = l + n;
-      else if (l + n == track) track = e;
-    }
-    // pivot(e, l), LPState.java:133-181.  piv, pc and b[l] are read here by every thread; their new values are stored
-    // behind barrier B1 only
-    const double piv = col[l], pc = c[e];
-    const double bl = __ddiv_rn(b[l], piv);                                         // :146
-    double* const prow = A + l * ld;
-    double ce_new = 0.0;
-    ent = rr_none();
-    for (int j = tid; j < n; j += T) {
-      if (j == e) {
-        prow[j] = __ddiv_rn(1.0, piv);                                              // :139
-        ce_new = -__ddiv_rn(pc, piv);                                               // :172
-        batch_consider(ent, ce_new, j, dantzig);
-      } else {
-        const double pr = __ddiv_rn(prow[j], piv);                                  // :144
-        const double cn = submul(c[j], pc, pr);                                     // :177
-        prow[j] = pr;
-        c[j] = cn;
-        batch_consider(ent, cn, j, dantzig);
-      }
-    }
-    ent = batch_reduce(ent, sh_e, lane, wave, nw);                                  // barrier B1
-    if (tid == e % T) c[e] = ce_new;
-    if (tid == 0) {
-      b[l] = bl;
-      *vp = addmul(*vp, bl, pc);                                                    // :171
-      const int32_t pe = perm[e];                                                   // exchangeIndexes :311-320
-      perm[e] = perm[n + l];
-      perm[n + l] = pe;
-    }
-    for (int i = tid; i < m; i += T) {
-      if (i == l) continue;
-      const double ce = col[i];
-      A[i * ld + e] = -__ddiv_rn(ce, piv);                                          // :157
-      b[i] = submul(b[i], ce, bl);                                                  // :164
-    }
-    for (int u = wave; u < nq * groups; u += nw) {
-      const int j = ((u % nq) << 6) + lane;
-      if (j >= n || j == e) continue;
-      const double pr = prow[j];
-      double* const Aj = A + j;
-      const int g = groups;
-      int i = u / nq;
-      for (; i + 3 * g < m; i += 4 * g) {                                           // :162, four rows in flight
-        const int i0 = i, i1 = i + g, i2 = i + 2 * g, i3 = i + 3 * g;
-        const double c0 = col[i0], c1 = col[i1], c2 = col[i2], c3 = col[i3];
-        const double x0 = submul(Aj[i0 * ld], c0, pr), x1 = submul(Aj[i1 * ld], c1, pr);
-        const double x2 = submul(Aj[i2 * ld], c2, pr), x3 = submul(Aj[i3 * ld], c3, pr);
-        if (i0 != l) Aj[i0 * ld] = x0;
-        if (i1 != l) Aj[i1 * ld] = x1;
-        if (i2 != l) Aj[i2 * ld] = x2;
-        if (i3 != l) Aj[i3 * ld] = x3;
-      }
-      for (; i < m; i += g)
-        if (i != l) Aj[i * ld] = submul(Aj[i * ld], col[i], pr);
-    }
-    pivots++;
-    __syncthreads();                                                                // barrier B2
-  }
+  const RatioRow ent = batch_entering(S);
+  const int status = batch_loop(S, ent, a.max_pivots, pivots, track);
   __syncthreads();
   for (int q = tid; q < nvec; q += T) ((d2*)image)[q] = ((const d2*)batch_lds)[q];
   if (tid == 0) {
     a.status[k] = status;
     a.pivots[k] = pivots;
     a.track[k] = track;
+  }
+}
+
+// k_batch_solve: the whole of LPSolver.solve (LPSolver.java:78-133) for MANY SMALL standard forms in one launch, one
+// workgroup per form.  What it adds around the loop above, all of it on chip and per LP:
+//   load       `min` negates c (:86-89, exact); minInB (:375-386) is one workgroup reduction on (b[i], i) from 1e50, so a
+//              NaN or a value >= 1e50 is never chosen; no index or a minimum >= 0: the loop alone, as k_batch_simplex
+//   aux LP     convertIntoAuxLP (:283-321): A at the pitch of n + 1 columns with column n = -1, c = 0 but c[n] = -1,
+//              v = 0, perm = originals | x0 (id n + m) | slacks; c0 stays in LDS for the restore
+//   phase 1    the forced pivot (n, minInB) (:138, made whatever the budget), the loop with x0 tracked (:142-157; UNBOUNDED
+//              here is LPX_AUX_UNBOUNDED), handleInitialization (:166-180: x0 basic with |b[row]| > 1e-9 is LPX_INFEASIBLE)
+//              and the degenerate pivot (:182-198) at the first slot with |A[row][i]| > 1e-9, found by a workgroup minimum
+//              on the index; it counts in pivots_phase1 and is not held against the budget (as lpx_solve has it)
+//   restore    restoreInitialLP (:200-246) bug for bug, as lpx_restore_initial_lp / k_restore_objective have it: an
+//              ordered original variable that is nonbasic at aux slot n is LPX_RESTORE_INDEX_FAULT and leaves the auxiliary
+//              state as it is; otherwise x0's column is dropped, thread j accumulates c[j] over the entries in order with
+//              the same addmul / __dadd_rn sequence, one thread accumulates v, and perm loses x0's slot
+//   phase 2    the loop on the restored m x n LP, budget max(0, max_pivots - pivots_phase1)
+// and the final image goes back to HBM: m x n, or the m x (n + 1) auxiliary LP when the solve ended inside phase 1.
+// Nothing is shared between workgroups.  The one-off shifts (column drop, perm) are done by single waves on whole rows:
+// a wave reads a 64-entry chunk and then writes it one place to the left, chunks in increasing order.
+
+// row[j] = row[j + 1] for from <= j < len - 1, by ONE wave
+template <typename V>
+__device__ __forceinline__ void batch_wave_shift_left(V* row, int from, int len, int lane) {
+  for (int base = from; base < len - 1; base += 64) {
+    const int j = base + lane;
+    V x = V(0);
+    if (j + 1 < len) x = row[j + 1];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // no instruction: the compiler keeps the chunk's reads in
+    __builtin_amdgcn_wave_barrier();                         // front of its writes, and a wave runs them in that order
+    if (j + 1 < len) row[j] = x;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void k_batch_solve(const BatchSolveArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double batch_lds[];
+  const int k = blockIdx.x;
+  if (k >= a.count) return;
+  const int m = a.m[k], n = a.n[k], na = n + 1;
+  const BatchLayout L0 = batch_layout(m, n);
+  const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = T >> 6;
+  double* const image = a.image + a.offset[k];
+  const bool maximize = a.maximize == nullptr || a.maximize[k] != 0;
+
+  // minInB straight from the HBM image; the front of the LDS (every launch has at least kBatchScratchBytes) is the scratch
+  RatioRow mb = rr_none();
+  for (int i = tid; i < m; i += T) {
+    const double bi = image[L0.b + i];
+    if (bi < kInf) mb = rr_min(mb, RatioRow{bi, i, 0});
+  }
+  mb = batch_reduce(mb, (RatioRow*)batch_lds, lane, wave, nw);
+  const int mib = mb.row;
+  const bool phase1 = mib != INT_MAX && mb.ratio < 0.0;                             // LPSolver.java:119
+  const BatchSolveLayout W = batch_solve_layout(m, n);
+  const BatchLayout L = phase1 ? W.aux : L0;
+  // the host sized the launch and the image room with the same rule from the same b: never taken, and never out of bounds
+  if ((phase1 ? W.lds_bytes : L0.lds_bytes) > a.lds_bytes || phase1 != (a.phase1[k] != 0)) {
+    if (tid == 0) {
+      a.status[k] = 7 /* LPX_DEVICE_ERROR */;
+      a.phase1_used[k] = 0; a.x0_slot[k] = -1; a.n_final[k] = n; a.pivots1[k] = 0; a.pivots2[k] = 0; a.v[k] = 0.0;
+    }
+    return;
+  }
+  __syncthreads();   // the scratch has been read
+
+  BatchLp S;
+  S.A = batch_lds;
+  S.b = batch_lds + L.b;
+  S.c = batch_lds + L.c;
+  S.vp = batch_lds + L.v;
+  S.perm = (int32_t*)(batch_lds + L.perm);
+  S.col = batch_lds + L.col;
+  S.sh_e = (RatioRow*)(S.col + ((m + 1) & ~1));
+  S.sh_l = S.sh_e + 16;
+  S.ld = (int)L.ld; S.m = m; S.n = phase1 ? na : n;
+  S.tid = tid; S.T = T; S.lane = lane; S.wave = wave; S.nw = nw;
+  S.dantzig = a.dantzig;
+
+  int status = 0;
+  int64_t pivots1 = 0, pivots2 = 0;
+  int x0 = -1, n_final = n, none = -1;
+  if (!phase1) {
+    // convertIntoSlackForm (:248-272): the image as it is, c negated for `min`
+    const int nvec = (int)(L0.image >> 1);
+    for (int q = tid; q < nvec; q += T) ((d2*)batch_lds)[q] = ((const d2*)image)[q];
+    __syncthreads();
+    if (!maximize)
+      for (int j = tid; j < n; j += T) S.c[j] = -S.c[j];                            // :86-89
+    __syncthreads();
+    status = batch_loop(S, batch_entering(S), a.max_pivots, pivots2, none);         // :96-114
+    __syncthreads();
+    for (int q = tid; q < nvec; q += T) ((d2*)image)[q] = ((const d2*)batch_lds)[q];
+  } else {
+    double* const c0 = batch_lds + W.c0;
+    int32_t* const order = (int32_t*)(batch_lds + W.order);
+    int32_t* const slot_of = (int32_t*)(batch_lds + W.slot);
+    const int n_ord = a.order_len[k];
+    const int32_t* const g_order = a.order + (int64_t)k * a.order_pitch;
+    const int ld0 = (int)L0.ld, ld = S.ld;
+    // convertIntoAuxLP (:283-321)
+    for (int i = wave; i < m; i += nw) {
+      for (int j = lane; j < n; j += 64) S.A[i * ld + j] = image[(int64_t)i * ld0 + j];
+      if (lane == 0) S.A[i * ld + n] = -1.0;                                        // :293
+    }
+    for (int i = tid; i < m; i += T) S.b[i] = image[L0.b + i];
+    for (int j = tid; j < n; j += T) {
+      const double cj = image[L0.c + j];
+      c0[j] = maximize ? cj : -cj;                                                  // :86-89
+      S.c[j] = 0.0;                                                                 // :299-301
+      if (j < n_ord) order[j] = g_order[j];
+    }
+    if (tid == 0) { S.c[n] = -1.0; *S.vp = 0.0; }
+    for (int s = tid; s < na + m; s += T) S.perm[s] = s < n ? s : s == n ? n + m : s - 1;
+    __syncthreads();
+
+    // solveAuxLP (:135-164)
+    batch_save_column(S, n);
+    RatioRow ent = batch_pivot(S, n, mib);                                          // :138
+    pivots1 = 1;
+    x0 = mib + na;                                                                  // :139
+    const int64_t lim1 = a.max_pivots < 0 ? -1 : (a.max_pivots > 1 ? a.max_pivots - 1 : 0);
+    int64_t done = 0;
+    status = batch_loop(S, ent, lim1, done, x0);
+    pivots1 += done;
+    if (status == 1) status = 3 /* LPX_AUX_UNBOUNDED */;                            // :147-150
+    __syncthreads();
+    n_final = na;
+    if (status == 0 && x0 >= na) {
+      const int row = x0 - na;
+      if (fabs(S.b[row]) > kEps) status = 2 /* LPX_INFEASIBLE */;                   // handleInitialization :171-174
+      else {
+        RatioRow first = rr_none();                                                 // performDegeneratePivot :182-198
+        for (int i = tid; i < na; i += T)
+          if (fabs(S.A[row * ld + i]) > kEps) first = rr_min(first, RatioRow{0.0, i, 0});
+        first = batch_reduce(first, S.sh_l, lane, wave, nw);
+        if (first.row == INT_MAX) status = 4 /* LPX_NO_DEGENERATE_PIVOT */;         // :192-194
+        else {
+          batch_save_column(S, first.row);
+          batch_pivot(S, first.row, row);                                           // :195
+          pivots1++;
+          x0 = first.row;
+        }
+      }
+    }
+    if (status == 0) {
+      // restoreInitialLP (:200-246).  auxLP.coefficients first: the slot of every original variable
+      for (int s = tid; s < na + m; s += T) {
+        const int32_t id = S.perm[s];
+        if (id >= 0 && id < n) slot_of[id] = s;
+      }
+      // :231 with cur = n is the reference's ArrayIndexOutOfBoundsException: only the variable in slot n can raise it
+      const int32_t at_n = S.perm[n];
+      RatioRow fault = rr_none();
+      if (at_n >= 0 && at_n < n)
+        for (int t = tid; t < n_ord; t += T)
+          if (order[t] == at_n) fault = rr_min(fault, RatioRow{0.0, t, 0});
+      fault = batch_reduce(fault, S.sh_e, lane, wave, nw);
+      if (fault.row != INT_MAX) status = 6 /* LPX_RESTORE_INDEX_FAULT */;
+    }
+    if (status == 0) {
+      for (int i = wave; i < m; i += nw) batch_wave_shift_left(S.A + i * ld, x0, na, lane);          // :208-211
+      __syncthreads();
+      for (int j = tid; j < n; j += T) {                                            // :213-233, as k_restore_objective
+        double acc = 0.0;
+        for (int t = 0; t < n_ord; ++t) {
+          const int32_t index = order[t];
+          const int cur = slot_of[index];                                           // :220
+          const double kk = c0[index];                                              // :219
+          if (cur >= na) {
+            const double coef = -S.A[(cur - na) * ld + j];                          // :226
+            acc = addmul(acc, coef, kk);                                            // :227
+          } else if (cur == j) {
+            acc = __dadd_rn(acc, kk);                                               // :231 (an aux-LP slot as a post-drop index)
+          }
+        }
+        S.c[j] = acc;
+      }
+      if (tid == T - 1) {
+        double v = 0.0;
+        for (int t = 0; t < n_ord; ++t) {
+          const int32_t index = order[t];
+          const int cur = slot_of[index];
+          if (cur >= na) v = addmul(v, S.b[cur - na], c0[index]);                   // :223
+        }
+        *S.vp = v;
+      }
+      if (wave == 0) batch_wave_shift_left(S.perm, x0, na + m, lane);               // :235-244
+      __syncthreads();
+      S.n = n;
+      n_final = n;
+      const int64_t lim2 = a.max_pivots < 0 ? -1 : (a.max_pivots > pivots1 ? a.max_pivots - pivots1 : 0);
+      status = batch_loop(S, batch_entering(S), lim2, pivots2, none);               // :96-114
+      __syncthreads();
+    }
+    if (n_final == na) {   // ended inside phase 1: the front of the LDS IS the image of the m x (n + 1) auxiliary LP
+      const int nvec = (int)(L.image >> 1);
+      for (int q = tid; q < nvec; q += T) ((d2*)image)[q] = ((const d2*)batch_lds)[q];
+    } else {               // m x n at the auxiliary pitch: entry by entry into batch_layout(m, n)
+      for (int i = wave; i < m; i += nw)
+        for (int j = lane; j < n; j += 64) image[(int64_t)i * ld0 + j] = S.A[i * ld + j];
+      for (int i = tid; i < m; i += T) image[L0.b + i] = S.b[i];
+      for (int j = tid; j < n; j += T) image[L0.c + j] = S.c[j];
+      if (tid == 0) image[L0.v] = *S.vp;
+      int32_t* const g_perm = (int32_t*)(image + L0.perm);
+      for (int s = tid; s < n + m; s += T) g_perm[s] = S.perm[s];
+    }
+  }
+  if (tid == 0) {
+    a.status[k] = status;
+    a.phase1_used[k] = phase1 ? 1 : 0;
+    a.x0_slot[k] = x0;
+    a.n_final[k] = n_final;
+    a.pivots1[k] = pivots1;
+    a.pivots2[k] = pivots2;
+    a.v[k] = *S.vp;
   }
 }
 
@@ -181,6 +441,31 @@ int batch_blocks_per_cu(int threads, int lds_bytes) {
   if (threads <= 64) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_simplex<64>, threads, (size_t)lds_bytes);
   else if (threads <= 256) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_simplex<256>, threads, (size_t)lds_bytes);
   else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_simplex<1024>, threads, (size_t)lds_bytes);
+  if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
+  return nb;
+}
+
+template <int kThreads>
+static hipError_t batch_solve_launch_t(const BatchSolveArgs& a, hipStream_t s) {
+  (void)hipFuncSetAttribute((const void*)k_batch_solve<kThreads>, hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_batch_solve<kThreads>, dim3(a.count), dim3(a.threads), (size_t)a.lds_bytes, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_solve(const BatchSolveArgs& a, hipStream_t s) {
+  if (a.count <= 0) return hipSuccess;
+  if (a.threads <= 64) return batch_solve_launch_t<64>(a, s);
+  if (a.threads <= 256) return batch_solve_launch_t<256>(a, s);
+  return batch_solve_launch_t<1024>(a, s);
+}
+
+int batch_solve_blocks_per_cu(int threads, int lds_bytes) {
+  int nb = 0;
+  hipError_t e;
+  if (threads <= 64) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_solve<64>, threads, (size_t)lds_bytes);
+  else if (threads <= 256) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_solve<256>, threads, (size_t)lds_bytes);
+  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_solve<1024>, threads, (size_t)lds_bytes);
   if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
   return nb;
 }

@@ -88,6 +88,12 @@ hipError_t launch_batch_simplex(const BatchArgs& a, hipStream_t s) {
 int batch_blocks_per_cu(int threads, int lds_bytes) {
   return std::min(plain::batch_blocks_per_cu(threads, lds_bytes), fused::batch_blocks_per_cu(threads, lds_bytes));
 }
+hipError_t launch_batch_solve(const BatchSolveArgs& a, hipStream_t s) {
+  return a.fused ? fused::launch_batch_solve(a, s) : plain::launch_batch_solve(a, s);
+}
+int batch_solve_blocks_per_cu(int threads, int lds_bytes) {
+  return std::min(plain::batch_solve_blocks_per_cu(threads, lds_bytes), fused::batch_solve_blocks_per_cu(threads, lds_bytes));
+}
 void launch_transpose(const double* dA, int64_t lda, double* dAt, int64_t ldat, int m, int n, hipStream_t s) {
   plain::launch_transpose(dA, lda, dAt, ldat, m, n, s);
 }

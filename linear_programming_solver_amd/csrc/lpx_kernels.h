@@ -157,6 +157,49 @@ struct BatchArgs {
   int32_t lds_bytes;       // dynamic LDS of the launch: the largest batch_layout(m, n).lds_bytes of the batch
   int32_t threads;         // workgroup size (multiple of 64, <= 1024)
 };
+// k_batch_solve (LPSolver.solve per workgroup): the LDS of an m x n LP that TAKES PHASE 1.  The workgroup then works in
+// the image of the m x (n + 1) auxiliary LP (`aux`, with its saved column and reduction scratch) for the whole solve —
+// after restoreInitialLP the tableau keeps the auxiliary pitch, one column narrower — and keeps behind it what
+// restoreInitialLP needs: c0[n] (the form's c, negated for `min`), the restore order int32[n] and the slot of every
+// original variable int32[n].  An LP that needs no phase 1 takes batch_layout(m, n) as in k_batch_simplex.
+struct BatchSolveLayout {
+  BatchLayout aux;
+  int64_t c0, order, slot;   // offsets in doubles (order, slot: of their first int32)
+  int64_t lds_bytes;
+};
+__host__ __device__ inline BatchSolveLayout batch_solve_layout(int64_t m, int64_t n) {
+  BatchSolveLayout W;
+  W.aux = batch_layout(m, n + 1);
+  W.c0 = W.aux.lds_bytes / 8;
+  W.order = W.c0 + ((n + 1) & ~(int64_t)1);
+  W.slot = W.order + (n + 1) / 2;
+  W.lds_bytes = 8 * (W.order + ((n + 1) & ~(int64_t)1));
+  return W;
+}
+struct BatchSolveArgs {
+  int32_t count;
+  const int32_t* m;          // [count]
+  const int32_t* n;          // [count] columns of the standard form
+  const int64_t* offset;     // [count] first double of LP k's image; an LP with phase1[k] has room for batch_layout(m, n + 1)
+  double* image;             // in: batch_layout(m, n); out: batch_layout(m, n_final)
+  const int32_t* maximize;   // [count] or NULL: every LP is a maximisation
+  const int32_t* phase1;     // [count] what the host found with minInB: it sized the image room and the LDS from it
+  const int32_t* order;      // [count * order_pitch] restore order of LP k (original-variable indices)
+  const int32_t* order_len;  // [count] its entries (<= n)
+  int64_t order_pitch;
+  int32_t* status;           // [count] out: lpx_status
+  int32_t* phase1_used;      // [count] out
+  int32_t* x0_slot;          // [count] out: -1 without phase 1
+  int32_t* n_final;          // [count] out: n, or n + 1 when the solve ended inside phase 1
+  int64_t* pivots1;          // [count] out
+  int64_t* pivots2;          // [count] out
+  double* v;                 // [count] out: the objective constant of the final state
+  int64_t max_pivots;        // budget of the whole solve per LP; < 0: unlimited
+  int32_t dantzig;
+  int32_t fused;
+  int32_t lds_bytes;
+  int32_t threads;
+};
 
 // ---- launch wrappers --------------------------------------------------------------------------------------------
 // lpx_kernels.hip is compiled twice: plain (one rounding per reference operation) and fused (updates as one FMA).

@@ -73,4 +73,7 @@ void launch_checksum(const Buffers& B, int m_local, int n, int row0, unsigned lo
 hipError_t launch_batch_simplex(const BatchArgs& a, hipStream_t s);
 // workgroups of that launch one CU holds at once (occupancy API; 0 on error)
 int batch_blocks_per_cu(int threads, int lds_bytes);
+// batched solve with phase 1 on chip: LPSolver.solve for a.count LPs in one launch (k_batch_solve, lpx_batch.inc)
+hipError_t launch_batch_solve(const BatchSolveArgs& a, hipStream_t s);
+int batch_solve_blocks_per_cu(int threads, int lds_bytes);
 void launch_transpose(const double* dA, int64_t lda, double* dAt, int64_t ldat, int m, int n, hipStream_t s);

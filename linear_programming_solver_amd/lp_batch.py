@@ -110,12 +110,71 @@ class LPBatch:
             raise_for_status(rc)
         return st, piv, tr
 
+    def solve(self, maximize=None, max_pivots=-1, restore_orders=None):
+        """LPSolver.solve for every LP of the batch in ONE launch, phase 1 included (lpx_batch_solve); the batch must be
+        as created from standard forms (A, b, c).  maximize: one flag per LP (None: every LP maximises).
+        restore_orders: None (the default-name order for every LP) or one entry per LP, each None or the order of
+        restoreInitialLP as original-variable indices (at most n of them; an empty one substitutes nothing).  Returns a
+        list of SolveInfo; .perm and .x are filled when the LP's final state is m x n and None when the solve ended
+        inside phase 1 (LPBatch.read(k) then gives the auxiliary LP)."""
+        from .lp_solver import SolveInfo
+        cnt = self.count
+        n_max = int(self.n.max()) if cnt else 0
+        mx = None
+        if maximize is not None:
+            mx = np.ascontiguousarray(np.asarray([1 if f else 0 for f in maximize], dtype=np.int32))
+            if mx.shape != (cnt,):
+                raise ValueError("maximize needs one flag per LP")
+        order = olen = None
+        if restore_orders is not None:
+            if len(restore_orders) != cnt:
+                raise ValueError("restore_orders needs one entry per LP")
+
+            def default_name_order(n):
+                out = np.zeros(max(n, 1), dtype=np.int32)
+                self._L.lpx_java_default_name_order(n, out.ctypes.data_as(_lib.ip))
+                return out[:n]
+            order = np.zeros((cnt, max(n_max, 1)), dtype=np.int32)
+            olen = np.zeros(cnt, dtype=np.int32)
+            for k, o in enumerate(restore_orders):
+                o = default_name_order(int(self.n[k])) if o is None else np.asarray(o, dtype=np.int32).reshape(-1)
+                if o.size > int(self.n[k]):
+                    raise ValueError("restore order of LP %d has %d entries for %d variables" % (k, o.size, self.n[k]))
+                order[k, :o.size] = o
+                olen[k] = o.size
+        res = (_lib.SolveResult * max(cnt, 1))()
+        rc = self._L.lpx_batch_solve(self._h, None if mx is None else _ip(mx), int(max_pivots),
+                                     None if order is None else order.ctypes.data_as(_lib.ip),
+                                     None if olen is None else _ip(olen), res)
+        if rc:
+            raise_for_status(rc)
+        m_max = int(self.m.max()) if cnt else 0
+        x = np.zeros((cnt, max(n_max, 1)))
+        perm = np.full((cnt, max(n_max + m_max, 1)), -1, dtype=np.int32)   # -1 stays where the final state is not m x n
+        rc = self._L.lpx_batch_solutions(self._h, x.ctypes.data_as(_lib.dp), perm.ctypes.data_as(_lib.ip))   # one read-back
+        if rc:
+            raise_for_status(rc)
+        infos = []
+        for k in range(cnt):
+            m, n = int(self.m[k]), int(self.n[k])
+            written = n + m == 0 or perm[k, 0] >= 0
+            infos.append(SolveInfo(res[k], perm[k, :n + m].copy() if written else None, x[k, :n].copy() if written else None))
+        return infos
+
+    def shape(self, k):
+        """(m, n) of LP k now: n + 1 columns after a solve() that ended inside phase 1."""
+        m, n = C.c_int32(), C.c_int32()
+        rc = self._L.lpx_batch_shape(self._h, int(k), C.byref(m), C.byref(n))
+        if rc:
+            raise_for_status(rc)
+        return m.value, n.value
+
     def read(self, k):
         """(A, b, c, v, perm) of LP k, like LPState.read()."""
         k = int(k)
         if not 0 <= k < self.count:
             raise IndexError("LP %d of a batch of %d" % (k, self.count))
-        m, n = int(self.m[k]), int(self.n[k])
+        m, n = self.shape(k)
         A = np.zeros((m, n))
         b = np.zeros(m)
         c = np.zeros(n)

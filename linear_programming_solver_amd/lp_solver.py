@@ -46,6 +46,7 @@ class LPSolver:
         self.last = None
         self.last_batch = None            # solve_batch: one SolveInfo per form
         self.last_batch_in_kernel = 0     # ... and how many of the forms the batch kernel solved
+        self.last_batch_x = None          # solve_batch(phase1="kernel"): x* per form, None where the state is not m x n
 
     def _arith_options(self):
         return {} if self.fused is None else {"fused": int(self.fused)}
@@ -93,13 +94,21 @@ class LPSolver:
             raise_for_status(rc)
         return Decimal(res.objective_text.decode())
 
-    def solve_batch(self, forms):
+    def solve_batch(self, forms, phase1="host"):
         """LPSolver.solve for many small forms at once (lpx_solve_batch): the forms that need no phase 1 (min b >= 0)
         are solved together by ONE launch of the batch kernel, the others one by one.  Returns a list with one entry
         per form: the Decimal solve() would return, or the exception INSTANCE solve() would raise (the reference's
         class and message) — returned, not raised, so one unbounded form does not hide the others.  self.last_batch
         holds a SolveInfo per form, self.last_batch_in_kernel how many forms the batch kernel took.  Every form must
-        fit the batch kernel (lpx_batch_lds_bytes); single device only."""
+        fit the batch kernel (lpx_batch_lds_bytes); single device only.
+
+        phase1="kernel": the forms that need phase 1 stay in the batch kernel too (lpx_solve_batch_all; a NAMED one
+        through lpx_batch_solve with the key-set order of its own names), as long as their auxiliary LP fits
+        (lpx_batch_solve_lds_bytes); self.last_batch carries perm and x per form and self.last_batch_x the solutions."""
+        if phase1 not in ("host", "kernel"):
+            raise ValueError('phase1 is "host" or "kernel"')
+        if phase1 == "kernel":
+            return self._solve_batch_in_kernel(list(forms))
         from .lp_batch import pack_lps
         L = _lib.lib()
         forms = list(forms)
@@ -139,6 +148,78 @@ class LPSolver:
                 answers[k] = Decimal(res[t].objective_text.decode()) if exc is None else exc
         self.last_batch = infos
         self.last_batch_in_kernel = int(in_kernel.value)
+        return answers
+
+    def _solve_batch_in_kernel(self, forms):
+        from .lp_batch import LPBatch, pack_lps
+        L = _lib.lib()
+        infos, answers = [None] * len(forms), [None] * len(forms)
+        in_kernel = 0
+
+        def needs_phase1(f):   # minInB's rule, as the library and the kernel apply it (a NaN is never the minimum)
+            mib = self.min_in_b(f.b)
+            return mib != -1 and f.b[mib] < 0.0
+
+        def answer(info):
+            exc = exception_for_status(info.status)
+            return Decimal(info.objective_text) if exc is None else exc
+
+        named, packed_idx = [], []
+        for k, f in enumerate(forms):
+            if f.has_variable_names() and f.n > 0 and needs_phase1(f):
+                if L.lpx_batch_solve_lds_bytes(f.m, f.n) <= _lib.BATCH_LDS_BYTES:
+                    named.append(k)
+                else:                                   # the auxiliary LP does not fit a workgroup: solve()
+                    try:
+                        answers[k] = self.solve(f)
+                    except Exception as exc:
+                        answers[k] = exc
+                    infos[k] = self.last
+            else:
+                packed_idx.append(k)
+        if named:   # each substitutes in the key-set order of its own names (restoreInitialLP)
+            batch = LPBatch([(forms[k].A, forms[k].b, forms[k].c) for k in named], device=self.device,
+                            options=self._arith_options(), pricing=self.pricing)
+            try:
+                got = batch.solve(maximize=[forms[k].maximize for k in named], max_pivots=self.max_pivots,
+                                  restore_orders=[self._key_set_order(forms[k]) for k in named])
+            finally:
+                batch.close()
+            for k, info in zip(named, got):
+                infos[k], answers[k] = info, answer(info)
+            in_kernel += len(named)
+        if packed_idx:
+            p = pack_lps([(forms[k].A, forms[k].b, forms[k].c) for k in packed_idx])
+            cnt, pw = p["count"], p["n_max"] + p["m_max"]
+            maxi = np.array([1 if forms[k].maximize else 0 for k in packed_idx], dtype=np.int32)
+            opts = _lib.SolveOptions()
+            opts.device = self.device
+            opts.max_pivots = self.max_pivots
+            opts.pricing = self.pricing
+            opts.fused = 0 if self.fused is None else (1 if self.fused else -1)
+            opts.restore_order_len = -1
+            res = (_lib.SolveResult * cnt)()
+            x = np.zeros((cnt, max(p["n_max"], 1)))
+            perm = np.full((cnt, max(pw, 1)), -1, dtype=np.int32)   # -1 stays where the final state is not m x n
+            took = C.c_int32(0)
+            rc = L.lpx_solve_batch_all(cnt, p["m_max"], p["n_max"], p["m"].ctypes.data_as(_lib.ip),
+                                       p["n"].ctypes.data_as(_lib.ip), p["A"].ctypes.data_as(_lib.dp) if p["A"].size else None,
+                                       p["lda"], p["strideA"], p["b"].ctypes.data_as(_lib.dp) if p["b"].size else None,
+                                       p["c"].ctypes.data_as(_lib.dp) if p["c"].size else None, maxi.ctypes.data_as(_lib.ip),
+                                       C.byref(opts), res, x.ctypes.data_as(_lib.dp), perm.ctypes.data_as(_lib.ip),
+                                       C.byref(took))
+            if rc:
+                raise_for_status(rc)
+            for t, k in enumerate(packed_idx):
+                m, n = int(p["m"][t]), int(p["n"][t])
+                written = n + m == 0 or perm[t, 0] >= 0
+                infos[k] = SolveInfo(res[t], perm[t, :n + m].copy() if written else None,
+                                     x[t, :n].copy() if written else None)
+                answers[k] = answer(infos[k])
+            in_kernel += int(took.value)
+        self.last_batch = infos
+        self.last_batch_in_kernel = in_kernel
+        self.last_batch_x = [info.x for info in infos]
         return answers
 
     @staticmethod
