@@ -1,6 +1,8 @@
-// Batched solve behind the C ABI (include/lpx.h): many small LPs in ONE launch of k_batch_simplex (lpx_batch.inc), one
-// workgroup per LP with the LP's whole state in LDS.  The handle keeps one HBM image per LP (lpxk::BatchLayout); every
-// argument is checked before the first device call, so a bad call answers LPX_BAD_ARGUMENT on a machine without a GPU too.
+// Batched solve behind the C ABI (include/lpx.h): many small LPs in ONE launch, one workgroup per LP with the LP's whole
+// state in LDS (lpx_batch.inc: k_batch_simplex runs the loop, k_batch_solve the whole of LPSolver.solve with phase 1).
+// The handle keeps one HBM image per LP (lpxk::BatchLayout).  lpx_solve_batch and lpx_solve_batch_all are built from one
+// set of pieces (Forms, check_one_shot, Gathered, solve_alone, stamp_seconds).  Every argument is checked before the first
+// device call, so a bad call answers LPX_BAD_ARGUMENT on a machine without a GPU too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,15 +49,6 @@ double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// minInB (LPSolver.java:375-386) finds an entry below 0: the form needs the auxiliary LP (:119)
-bool needs_phase1(const double* b, int32_t m) {
-  double mn = 1e50;
-  int idx = -1;
-  for (int i = 0; i < m; i++)
-    if (mn > b[i]) { mn = b[i]; idx = i; }
-  return !(idx == -1 || b[idx] >= 0.0);
-}
-
 int64_t solve_lds_bytes_of(int64_t m, int64_t n) {
   if (m < 0 || n < 0) return -1;
   if ((double)m * (double)((n + 1) | 1) > 1e12) return INT64_MAX;
@@ -68,6 +61,32 @@ int64_t lds_bytes_of(int64_t m, int64_t n) {
   return lpxk::batch_layout(m, n).lds_bytes;
 }
 
+// `count` LPs inside m_max x n_max as the ABI passes them: shapes (NULL: all m_max x n_max), A with row pitch lda and
+// strideA between LPs, b and c at the pitches m_max and n_max, and for the one-shot calls the `max` flags (NULL: all max)
+struct Forms {
+  int32_t count, m_max, n_max;
+  const int32_t *m, *n;
+  const double* A;
+  int64_t lda, strideA;
+  const double *b, *c;
+  const int32_t* maximize;
+  int32_t rows(int32_t k) const { return m ? m[k] : m_max; }
+  int32_t cols(int32_t k) const { return n ? n[k] : n_max; }
+  const double* A_of(int32_t k) const { return A ? A + (int64_t)k * strideA : nullptr; }
+  const double* b_of(int32_t k) const { return b ? b + (int64_t)k * m_max : nullptr; }
+  const double* c_of(int32_t k) const { return c ? c + (int64_t)k * n_max : nullptr; }
+  bool maximizes(int32_t k) const { return !maximize || maximize[k] != 0; }
+  // minInB (LPSolver.java:375-386) finds an entry below 0 in LP k's b: the form needs the auxiliary LP (:119)
+  bool phase1(int32_t k) const {
+    const double* bk = b_of(k);
+    double mn = 1e50;
+    int idx = -1;
+    for (int i = 0; i < rows(k); i++)
+      if (mn > bk[i]) { mn = bk[i]; idx = i; }
+    return !(idx == -1 || bk[idx] >= 0.0);
+  }
+};
+
 // Workgroup size of one LP: a wave per 64-column chunk times up to four row groups of at least 16 rows, at most 16
 // waves.  One wave (no workgroup barriers) up to 16 x 64; 256 threads for 64 x 64; 1024 from 64 x 256 or 49 x 200 on.
 int threads_of(int32_t m, int32_t n) {
@@ -76,16 +95,16 @@ int threads_of(int32_t m, int32_t n) {
   return 64 * std::min(16, nq * groups);
 }
 
-// shapes of a batch: every LP inside m_max x n_max and inside the LDS of one workgroup
-int check_shapes(const char* who, int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n) {
-  if (count < 0 || m_max < 0 || n_max < 0)
+// shapes of a batch: every LP inside m_max x n_max and inside the LDS of one workgroup; then the arrays those shapes read
+int check_forms(const char* who, const Forms& F) {
+  if (F.count < 0 || F.m_max < 0 || F.n_max < 0)
     return fail(LPX_BAD_ARGUMENT, std::string(who) + ": negative count or dimension");
-  if ((m == nullptr) != (n == nullptr)) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": m and n must both be given or both be NULL");
-  for (int32_t k = 0; k < count; k++) {
-    const int32_t mk = m ? m[k] : m_max, nk = n ? n[k] : n_max;
+  if ((F.m == nullptr) != (F.n == nullptr)) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": m and n must both be given or both be NULL");
+  for (int32_t k = 0; k < F.count; k++) {
+    const int32_t mk = F.rows(k), nk = F.cols(k);
     char msg[200];
-    if (mk < 0 || nk < 0 || mk > m_max || nk > n_max) {
-      snprintf(msg, sizeof msg, "%s: LP %d has shape %d x %d outside 0..%d x 0..%d", who, k, mk, nk, m_max, n_max);
+    if (mk < 0 || nk < 0 || mk > F.m_max || nk > F.n_max) {
+      snprintf(msg, sizeof msg, "%s: LP %d has shape %d x %d outside 0..%d x 0..%d", who, k, mk, nk, F.m_max, F.n_max);
       return fail(LPX_BAD_ARGUMENT, msg);
     }
     const int64_t need = lds_bytes_of(mk, nk);
@@ -95,20 +114,14 @@ int check_shapes(const char* who, int32_t count, int32_t m_max, int32_t n_max, c
       return fail(LPX_BAD_ARGUMENT, msg);
     }
   }
-  return 0;
-}
-
-int check_arrays(const char* who, int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n,
-                 const double* A, int64_t lda, int64_t strideA, const double* b, const double* c) {
   bool needA = false, needb = false, needc = false;
-  for (int32_t k = 0; k < count; k++) {
-    const int32_t mk = m ? m[k] : m_max, nk = n ? n[k] : n_max;
-    needA |= mk > 0 && nk > 0;
-    needb |= mk > 0;
-    needc |= nk > 0;
+  for (int32_t k = 0; k < F.count; k++) {
+    needA |= F.rows(k) > 0 && F.cols(k) > 0;
+    needb |= F.rows(k) > 0;
+    needc |= F.cols(k) > 0;
   }
-  if (lda < n_max || strideA < 0) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": lda < n_max or negative strideA");
-  if ((needA && !A) || (needb && !b) || (needc && !c)) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL array where data is due");
+  if (F.lda < F.n_max || F.strideA < 0) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": lda < n_max or negative strideA");
+  if ((needA && !F.A) || (needb && !F.b) || (needc && !F.c)) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL array where data is due");
   return 0;
 }
 
@@ -141,9 +154,8 @@ struct BatchGuard {
 };
 
 // the checked core of lpx_batch_create (no argument checks: the callers have made them)
-int create_checked(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m, const int32_t* n, const double* A,
-                   int64_t lda, int64_t strideA, const double* b, const double* c, const double* v, const int32_t* perm,
-                   int device, lpx_batch** out) {
+int create_checked(const Forms& F, const double* v, const int32_t* perm, int device, lpx_batch** out) {
+  const int32_t count = F.count, m_max = F.m_max, n_max = F.n_max;
   BatchGuard guard;
   lpx_batch* B = guard.B = new lpx_batch();
   B->device = device;
@@ -159,10 +171,10 @@ int create_checked(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m
   int64_t total = 0, lds = 0;
   int threads = 64, solve_threads = 64;
   for (int32_t k = 0; k < count; k++) {
-    B->m[k] = m ? m[k] : m_max;
-    B->n[k] = n ? n[k] : n_max;
+    B->m[k] = F.rows(k);
+    B->n[k] = F.cols(k);
     const lpxk::BatchLayout L = lpxk::batch_layout(B->m[k], B->n[k]);
-    B->need_p1[k] = B->m[k] > 0 && needs_phase1(b + (int64_t)k * m_max, B->m[k]);
+    B->need_p1[k] = F.phase1(k);
     B->offset[k] = total;
     // a form that needs phase 1 may come back from lpx_batch_solve as its m x (n + 1) auxiliary LP
     total += B->need_p1[k] ? std::max(L.image, lpxk::batch_layout(B->m[k], B->n[k] + 1).image) : L.image;
@@ -181,9 +193,9 @@ int create_checked(int32_t count, int32_t m_max, int32_t n_max, const int32_t* m
     const lpxk::BatchLayout L = lpxk::batch_layout(mk, nk);
     double* g = img.data() + B->offset[k];
     for (int32_t i = 0; i < mk; i++)
-      if (nk > 0) memcpy(g + (int64_t)i * L.ld, A + (int64_t)k * strideA + (int64_t)i * lda, (size_t)nk * sizeof(double));
-    if (mk > 0) memcpy(g + L.b, b + (int64_t)k * m_max, (size_t)mk * sizeof(double));
-    if (nk > 0) memcpy(g + L.c, c + (int64_t)k * n_max, (size_t)nk * sizeof(double));
+      if (nk > 0) memcpy(g + (int64_t)i * L.ld, F.A_of(k) + (int64_t)i * F.lda, (size_t)nk * sizeof(double));
+    if (mk > 0) memcpy(g + L.b, F.b_of(k), (size_t)mk * sizeof(double));
+    if (nk > 0) memcpy(g + L.c, F.c_of(k), (size_t)nk * sizeof(double));
     g[L.v] = v ? v[k] : 0.0;
     int32_t* p = (int32_t*)(g + L.perm);
     for (int32_t s = 0; s < nk + mk; s++) p[s] = perm ? perm[(int64_t)k * ((int64_t)n_max + m_max) + s] : s;
@@ -267,6 +279,131 @@ void fill_objective(lpx_solve_result& r, double v, bool maximize) {
   r.objective_rounded = strtod(r.objective_text, nullptr);
 }
 
+void init_results(lpx_solve_result* results, int32_t count) {
+  for (int32_t k = 0; k < count; k++) {
+    memset(&results[k], 0, sizeof results[k]);
+    results[k].x0_slot = -1;
+    results[k].status = LPX_BAD_ARGUMENT;
+  }
+}
+
+// the times of a call that began at t_start: the same in every result
+void stamp_seconds(lpx_solve_result* results, int32_t count, double t_start, double t_pivots) {
+  const double t_total = now_s() - t_start;
+  for (int32_t k = 0; k < count; k++) {
+    results[k].seconds_total = t_total;
+    results[k].seconds_pivots = t_pivots;
+  }
+}
+
+// every LP's image from ONE copy through the handle's stream
+int read_images(const lpx_batch* B, std::vector<double>& img) {
+  img.resize((size_t)B->offset[B->count]);
+  if (img.empty()) return 0;
+  HIP_TRY(hipSetDevice(B->device));
+  HIP_TRY(hipMemcpyAsync(img.data(), B->d_image, img.size() * sizeof(double), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipStreamSynchronize(B->stream));
+  return 0;
+}
+
+// x and perm of LP t of the handle, from the images read back, into row k of x_out and perm_out (either may be NULL); the
+// auxiliary LP of a solve that ended inside phase 1 does not hold the caller's variables: its rows stay as they are
+void write_solution(const lpx_batch* B, const std::vector<double>& img, int32_t t, int32_t k, double* x_out, int32_t* perm_out) {
+  const int32_t mt = B->m[t], nt = B->n[t];
+  if (B->n_cur[t] != nt) return;
+  const lpxk::BatchLayout L = lpxk::batch_layout(mt, nt);
+  const double* g = img.data() + B->offset[t];
+  const int32_t* fp = (const int32_t*)(g + L.perm);
+  if (perm_out && nt + mt > 0) memcpy(perm_out + k * ((int64_t)B->n_max + B->m_max), fp, ((size_t)nt + mt) * sizeof(int32_t));
+  if (!x_out) return;
+  double* x = x_out + (int64_t)k * B->n_max;
+  for (int32_t j = 0; j < nt; j++) x[j] = 0.0;
+  for (int32_t i = 0; i < mt; i++) {
+    const int32_t id = fp[(size_t)nt + i];
+    if (id >= 0 && id < nt) x[id] = g[L.b + i];
+  }
+}
+
+int launch_info(const char* who, lpx_batch* B, bool solve, int32_t* threads, int32_t* lds_bytes, int32_t* blocks_per_cu) {
+  if (!B) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL handle");
+  DeviceRestore keep_device;
+  HIP_TRY(hipSetDevice(B->device));
+  const int t = threads_in_effect(B, solve);
+  const int lds = solve ? (int)std::min<int64_t>(solve_launch_lds(B), INT32_MAX) : B->lds_bytes;
+  if (threads) *threads = t;
+  if (lds_bytes) *lds_bytes = lds;
+  if (blocks_per_cu) *blocks_per_cu = solve ? lpxk::batch_solve_blocks_per_cu(t, lds) : lpxk::batch_blocks_per_cu(t, lds);
+  return 0;
+}
+
+// The argument checks of a one-shot call in their order: shapes, arrays, results (and the flags where maximize_due), then
+// the options into `o` (NULL: the defaults) without what a batch cannot honour; `field` is how `who` names those.
+int check_one_shot(const char* who, const Forms& F, bool maximize_due, const lpx_solve_result* results, const char* field,
+                   const lpx_solve_options* opts, lpx_solve_options& o) {
+  if (int rc = check_forms(who, F)) return rc;
+  if (F.count > 0 && (!results || (maximize_due && !F.maximize)))
+    return fail(LPX_BAD_ARGUMENT, std::string(who) + (maximize_due ? ": results or maximize is NULL" : ": results is NULL"));
+  o = lpx_solve_options{};
+  o.max_pivots = -1;
+  if (opts) o = *opts;
+  const std::string f(field);
+  if (o.keep_state || o.perm_out || o.x_out)
+    return fail(LPX_BAD_ARGUMENT, std::string(who) + ": " + f + "keep_state, " + f + "perm_out and " + f + "x_out must be NULL");
+  if (o.device < 0 || (o.pricing != 0 && o.pricing != 1)) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": bad device or pricing");
+  return 0;
+}
+
+// The forms `index` names, gathered into dense arrays of their own (G): A rows copied from where they are, b and c as
+// they are -- but negate_c_for_min: c0 = -c for a `min` form (LPSolver.java:86-89) on the host, for the kernel that knows no `min`
+struct Gathered {
+  std::vector<int32_t> m, n;
+  std::vector<double> A, b, c;
+  Forms G;
+  Gathered(const Gathered&) = delete;   // G points into the vectors
+
+  Gathered(const Forms& F, const std::vector<int32_t>& index, bool negate_c_for_min) : m(index.size()), n(index.size()) {
+    const size_t nb = index.size(), ldp = std::max(F.n_max, 1), strideP = F.m_max * ldp;
+    A.assign(nb * strideP, 0.0);
+    b.assign(nb * F.m_max, 0.0);
+    c.assign(nb * F.n_max, 0.0);
+    for (size_t t = 0; t < nb; t++) {
+      const int32_t k = index[t];
+      m[t] = F.rows(k);
+      n[t] = F.cols(k);
+      const bool negate = negate_c_for_min && !F.maximizes(k);
+      for (int32_t i = 0; i < m[t]; i++) {
+        if (n[t] > 0) memcpy(&A[t * strideP + i * ldp], F.A_of(k) + (int64_t)i * F.lda, (size_t)n[t] * sizeof(double));
+        b[t * F.m_max + i] = F.b_of(k)[i];
+      }
+      for (int32_t j = 0; j < n[t]; j++) c[t * F.n_max + j] = negate ? -F.c_of(k)[j] : F.c_of(k)[j];
+    }
+    G = Forms{(int32_t)nb, F.m_max, F.n_max, m.data(), n.data(), A.data(), (int64_t)ldp, (int64_t)strideP, b.data(), c.data(), nullptr};
+  }
+
+  // the handle of the gathered forms, owned by `guard`
+  int create(const lpx_solve_options& o, BatchGuard& guard) const {
+    if (int rc = create_checked(G, nullptr, nullptr, o.device, &guard.B)) return rc;
+    guard.B->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
+    guard.B->pricing = o.pricing;
+    return 0;
+  }
+};
+
+// lpx_solve for the forms left out of the batch, into their results and their rows of x_out / perm_out (NULL: none)
+int solve_alone(const Forms& F, const std::vector<int32_t>& alone, const lpx_solve_options& o, lpx_solve_result* results,
+                double* x_out, int32_t* perm_out, double& t_pivots) {
+  const int64_t pw = (int64_t)F.n_max + F.m_max;
+  for (int32_t k : alone) {
+    lpx_solve_options oa = o;
+    oa.x_out = x_out ? x_out + (int64_t)k * F.n_max : nullptr;
+    oa.perm_out = perm_out ? perm_out + k * pw : nullptr;
+    const int rc = lpx_solve(F.rows(k), F.cols(k), F.A_of(k), F.lda, F.b_of(k), F.c_of(k), F.maximizes(k), &oa, &results[k]);
+    if (rc == LPX_DEVICE_ERROR || rc == LPX_BAD_ARGUMENT) return rc;
+    t_pivots += results[k].seconds_pivots;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int64_t lpx_batch_lds_bytes(int32_t m, int32_t n) {
@@ -286,11 +423,11 @@ extern "C" int lpx_batch_create(int32_t count, int32_t m_max, int32_t n_max, con
                                 const double* v, const int32_t* perm, int device, lpx_batch** out) {
   if (!out) return fail(LPX_BAD_ARGUMENT, "lpx_batch_create: out is NULL");
   *out = nullptr;
-  if (int rc = check_shapes("lpx_batch_create", count, m_max, n_max, m, n)) return rc;
-  if (int rc = check_arrays("lpx_batch_create", count, m_max, n_max, m, n, A, lda, strideA, b, c)) return rc;
+  const Forms F{count, m_max, n_max, m, n, A, lda, strideA, b, c, nullptr};
+  if (int rc = check_forms("lpx_batch_create", F)) return rc;
   if (device < 0) return fail(LPX_BAD_ARGUMENT, "lpx_batch_create: negative device");
   DeviceRestore keep_device;
-  return create_checked(count, m_max, n_max, m, n, A, lda, strideA, b, c, v, perm, device, out);
+  return create_checked(F, v, perm, device, out);
 }
 
 extern "C" void lpx_batch_destroy(lpx_batch* B) {
@@ -407,11 +544,7 @@ extern "C" int lpx_batch_solve(lpx_batch* B, const int32_t* maximize, int64_t ma
       if (nk > 0) lpx_java_default_name_order(nk, order.data() + (int64_t)k * pitch);
     }
   }
-  for (int32_t k = 0; k < count; k++) {
-    memset(&results[k], 0, sizeof results[k]);
-    results[k].x0_slot = -1;
-    results[k].status = LPX_BAD_ARGUMENT;
-  }
+  init_results(results, count);
   DeviceRestore keep_device;
   HIP_TRY(hipSetDevice(B->device));
   const size_t cnt = (size_t)count;
@@ -465,11 +598,7 @@ extern "C" int lpx_batch_solve(lpx_batch* B, const int32_t* maximize, int64_t ma
     fill_objective(r, h_v[k], !maximize || maximize[k] != 0);
     device_error |= r.status == LPX_DEVICE_ERROR;
   }
-  const double t_total = now_s() - t_start;
-  for (int32_t k = 0; k < count; k++) {
-    results[k].seconds_total = t_total;
-    results[k].seconds_pivots = t_pivots;
-  }
+  stamp_seconds(results, count, t_start, t_pivots);
   if (device_error) return fail(LPX_DEVICE_ERROR, "lpx_batch_solve: the kernel and the host disagree about an LP's layout");
   return 0;
 }
@@ -479,55 +608,20 @@ extern "C" int lpx_batch_solutions(lpx_batch* B, double* x_out, int32_t* perm_ou
   if (!B) return fail(LPX_BAD_ARGUMENT, "lpx_batch_solutions: NULL handle");
   if ((!x_out && !perm_out) || B->count == 0) return 0;
   DeviceRestore keep_device;
-  HIP_TRY(hipSetDevice(B->device));
-  std::vector<double> img((size_t)B->offset[B->count]);
-  if (!img.empty()) {
-    HIP_TRY(hipMemcpyAsync(img.data(), B->d_image, img.size() * sizeof(double), hipMemcpyDeviceToHost, B->stream));
-    HIP_TRY(hipStreamSynchronize(B->stream));
-  }
-  const int64_t pw = (int64_t)B->n_max + B->m_max;
-  for (int32_t k = 0; k < B->count; k++) {
-    const int32_t mk = B->m[k], nk = B->n[k];
-    if (B->n_cur[k] != nk) continue;   // the auxiliary LP of a solve that ended inside phase 1: not the caller's variables
-    const lpxk::BatchLayout L = lpxk::batch_layout(mk, nk);
-    const double* g = img.data() + B->offset[k];
-    const int32_t* fp = (const int32_t*)(g + L.perm);
-    if (perm_out && nk + mk > 0) memcpy(perm_out + k * pw, fp, ((size_t)nk + mk) * sizeof(int32_t));
-    if (x_out) {
-      double* x = x_out + (int64_t)k * B->n_max;
-      for (int32_t j = 0; j < nk; j++) x[j] = 0.0;
-      for (int32_t i = 0; i < mk; i++) {
-        const int32_t id = fp[(size_t)nk + i];
-        if (id >= 0 && id < nk) x[id] = g[L.b + i];
-      }
-    }
-  }
+  std::vector<double> img;
+  if (int rc = read_images(B, img)) return rc;
+  for (int32_t k = 0; k < B->count; k++) write_solution(B, img, k, k, x_out, perm_out);
   return 0;
 }
 
-// What the launch of lpx_batch_solve on this handle looks like (scripts/bench_batch.py): not part of include/lpx.h
-extern "C" int lpxi_batch_solve_launch_info(lpx_batch* B, int32_t* threads, int32_t* lds_bytes, int32_t* blocks_per_cu) {
-  if (!B) return fail(LPX_BAD_ARGUMENT, "lpxi_batch_solve_launch_info: NULL handle");
-  DeviceRestore keep_device;
-  HIP_TRY(hipSetDevice(B->device));
-  const int t = threads_in_effect(B, true);
-  const int lds = (int)std::min<int64_t>(solve_launch_lds(B), INT32_MAX);
-  if (threads) *threads = t;
-  if (lds_bytes) *lds_bytes = lds;
-  if (blocks_per_cu) *blocks_per_cu = lpxk::batch_solve_blocks_per_cu(t, lds);
-  return 0;
-}
-
-// What the launch of this handle looks like (scripts/bench_batch.py): not part of include/lpx.h
+// What the launch of lpx_batch_simplex_loop / of lpx_batch_solve on this handle looks like (scripts/bench_batch.py): not
+// part of include/lpx.h
 extern "C" int lpxi_batch_launch_info(lpx_batch* B, int32_t* threads, int32_t* lds_bytes, int32_t* blocks_per_cu) {
-  if (!B) return fail(LPX_BAD_ARGUMENT, "lpxi_batch_launch_info: NULL handle");
-  DeviceRestore keep_device;
-  HIP_TRY(hipSetDevice(B->device));
-  const int t = threads_in_effect(B);
-  if (threads) *threads = t;
-  if (lds_bytes) *lds_bytes = B->lds_bytes;
-  if (blocks_per_cu) *blocks_per_cu = lpxk::batch_blocks_per_cu(t, B->lds_bytes);
-  return 0;
+  return launch_info("lpxi_batch_launch_info", B, false, threads, lds_bytes, blocks_per_cu);
+}
+
+extern "C" int lpxi_batch_solve_launch_info(lpx_batch* B, int32_t* threads, int32_t* lds_bytes, int32_t* blocks_per_cu) {
+  return launch_info("lpxi_batch_solve_launch_info", B, true, threads, lds_bytes, blocks_per_cu);
 }
 
 // LPSolver.solve (LPSolver.java:78) for `count` standard forms.  The forms with min b >= 0 (no phase 1, :119) become one
@@ -538,88 +632,38 @@ extern "C" int lpx_solve_batch(int32_t count, int32_t m_max, int32_t n_max, cons
                                const int32_t* maximize, const lpx_solve_options* opts, lpx_solve_result* results,
                                int32_t* n_in_batch) {
   if (n_in_batch) *n_in_batch = 0;
-  if (int rc = check_shapes("lpx_solve_batch", count, m_max, n_max, m, n)) return rc;
-  if (int rc = check_arrays("lpx_solve_batch", count, m_max, n_max, m, n, A, lda, strideA, b, c)) return rc;
-  if (count > 0 && (!results || !maximize)) return fail(LPX_BAD_ARGUMENT, "lpx_solve_batch: results or maximize is NULL");
-  lpx_solve_options o{};
-  o.max_pivots = -1;
-  if (opts) o = *opts;
-  if (o.keep_state || o.perm_out || o.x_out)
-    return fail(LPX_BAD_ARGUMENT, "lpx_solve_batch: keep_state, perm_out and x_out must be NULL");
-  if (o.device < 0 || (o.pricing != 0 && o.pricing != 1)) return fail(LPX_BAD_ARGUMENT, "lpx_solve_batch: bad device or pricing");
+  const Forms F{count, m_max, n_max, m, n, A, lda, strideA, b, c, maximize};
+  lpx_solve_options o;
+  if (int rc = check_one_shot("lpx_solve_batch", F, true, results, "", opts, o)) return rc;
   const double t_start = now_s();
-  for (int32_t k = 0; k < count; k++) {
-    memset(&results[k], 0, sizeof results[k]);
-    results[k].x0_slot = -1;
-    results[k].status = LPX_BAD_ARGUMENT;
-  }
-  // which forms need no phase 1: minInB (:375-386) finds nothing below 0
+  init_results(results, count);
   std::vector<int32_t> in_batch, alone;
-  for (int32_t k = 0; k < count; k++) {
-    const int32_t mk = m ? m[k] : m_max;
-    const double* bk = mk > 0 ? b + (int64_t)k * m_max : nullptr;
-    double mn = 1e50;
-    int idx = -1;
-    for (int i = 0; i < mk; i++)
-      if (mn > bk[i]) { mn = bk[i]; idx = i; }
-    (idx == -1 || bk[idx] >= 0.0 ? in_batch : alone).push_back(k);
-  }
+  for (int32_t k = 0; k < count; k++) (F.phase1(k) ? alone : in_batch).push_back(k);
   double t_pivots = 0.0;
   const int32_t nb = (int32_t)in_batch.size();
   if (nb > 0) {
-    // gather the batch: shapes, A rows in place (lda, strideA), b, and c0 = +-c
-    std::vector<int32_t> bm(nb), bn(nb);
-    std::vector<double> bb((size_t)nb * m_max, 0.0), bc((size_t)nb * n_max, 0.0), bA;
-    const int64_t ldp = std::max(n_max, 1), strideP = (int64_t)m_max * ldp;
-    bA.assign((size_t)nb * strideP, 0.0);
-    for (int32_t t = 0; t < nb; t++) {
-      const int32_t k = in_batch[t];
-      bm[t] = m ? m[k] : m_max;
-      bn[t] = n ? n[k] : n_max;
-      for (int32_t i = 0; i < bm[t]; i++)
-        if (bn[t] > 0) memcpy(&bA[(size_t)t * strideP + (size_t)i * ldp], A + (int64_t)k * strideA + (int64_t)i * lda, (size_t)bn[t] * sizeof(double));
-      for (int32_t i = 0; i < bm[t]; i++) bb[(size_t)t * m_max + i] = b[(int64_t)k * m_max + i];
-      for (int32_t j = 0; j < bn[t]; j++) bc[(size_t)t * n_max + j] = maximize[k] ? c[(int64_t)k * n_max + j] : -c[(int64_t)k * n_max + j];
-    }
+    const Gathered G(F, in_batch, true);
     DeviceRestore keep_device;
     BatchGuard guard;
-    if (int rc = create_checked(nb, m_max, n_max, bm.data(), bn.data(), bA.data(), ldp, strideP, bb.data(), bc.data(), nullptr,
-                                nullptr, o.device, &guard.B))
-      return rc;
-    guard.B->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
-    guard.B->pricing = o.pricing;
+    if (int rc = G.create(o, guard)) return rc;
+    const lpx_batch* B = guard.B;
     std::vector<int64_t> done(nb);
     std::vector<int32_t> st(nb);
     const double t0 = now_s();
     if (int rc = lpx_batch_simplex_loop(guard.B, o.max_pivots < 0 ? -1 : o.max_pivots, done.data(), st.data(), nullptr)) return rc;
     t_pivots = now_s() - t0;
-    std::vector<double> img((size_t)guard.B->offset[nb]);
-    if (!img.empty()) HIP_TRY(hipMemcpy(img.data(), guard.B->d_image, img.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int32_t t = 0; t < nb; t++) {
+    std::vector<double> img;
+    if (int rc = read_images(B, img)) return rc;
+    for (int32_t t = 0; t < nb; t++) {   // the loop knows no phase 1: phase1_used, pivots_phase1 and x0_slot stay as initialised
       lpx_solve_result& r = results[in_batch[t]];
-      double v = img[(size_t)guard.B->offset[t] + lpxk::batch_layout(bm[t], bn[t]).v];
-      if (!maximize[in_batch[t]]) v = -v;                                             // :90
-      r.objective = v;
-      lpx_internal::round6_text(v, r.objective_text, sizeof r.objective_text);      // :113
-      r.objective_rounded = strtod(r.objective_text, nullptr);
+      fill_objective(r, img[(size_t)B->offset[t] + lpxk::batch_layout(G.m[t], G.n[t]).v], F.maximizes(in_batch[t]));
       r.pivots_phase2 = done[t];
       r.status = st[t];
     }
   }
   if (n_in_batch) *n_in_batch = nb;
-  lpx_solve_options oa = o;
-  for (int32_t k : alone) {
-    const int rc = lpx_solve(m ? m[k] : m_max, n ? n[k] : n_max, A ? A + (int64_t)k * strideA : nullptr, lda,
-                             b ? b + (int64_t)k * m_max : nullptr, c ? c + (int64_t)k * n_max : nullptr, maximize[k], &oa,
-                             &results[k]);
-    if (rc == LPX_DEVICE_ERROR || rc == LPX_BAD_ARGUMENT) return rc;
-    t_pivots += results[k].seconds_pivots;
-  }
-  const double t_total = now_s() - t_start;
-  for (int32_t k = 0; k < count; k++) {
-    results[k].seconds_total = t_total;
-    results[k].seconds_pivots = t_pivots;
-  }
+  if (int rc = solve_alone(F, alone, o, results, nullptr, nullptr, t_pivots)) return rc;
+  stamp_seconds(results, count, t_start, t_pivots);
   return 0;
 }
 
@@ -632,96 +676,52 @@ extern "C" int lpx_solve_batch_all(int32_t count, int32_t m_max, int32_t n_max, 
                                    double* x_out, int32_t* perm_out, int32_t* n_in_batch) {
   const char* who = "lpx_solve_batch_all";
   if (n_in_batch) *n_in_batch = 0;
-  if (int rc = check_shapes(who, count, m_max, n_max, m, n)) return rc;
-  if (int rc = check_arrays(who, count, m_max, n_max, m, n, A, lda, strideA, b, c)) return rc;
-  if (count > 0 && !results) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": results is NULL");
-  lpx_solve_options o{};
-  o.max_pivots = -1;
-  if (opts) o = *opts;
-  if (o.keep_state || o.perm_out || o.x_out)
-    return fail(LPX_BAD_ARGUMENT, std::string(who) + ": opts->keep_state, opts->perm_out and opts->x_out must be NULL");
-  if (o.device < 0 || (o.pricing != 0 && o.pricing != 1)) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": bad device or pricing");
+  const Forms F{count, m_max, n_max, m, n, A, lda, strideA, b, c, maximize};
+  lpx_solve_options o;
+  if (int rc = check_one_shot(who, F, false, results, "opts->", opts, o)) return rc;
   std::vector<int32_t> in_batch, alone;
   for (int32_t k = 0; k < count; k++) {
-    const int32_t mk = m ? m[k] : m_max, nk = n ? n[k] : n_max;
-    const bool p1 = mk > 0 && needs_phase1(b + (int64_t)k * m_max, mk);
+    const int32_t mk = F.rows(k), nk = F.cols(k);
+    const bool p1 = F.phase1(k);
     if (p1 && o.restore_order)
       if (int rc = check_order(who, k, mk, nk, o.restore_order, o.restore_order_len)) return rc;
     (p1 && solve_lds_bytes_of(mk, nk) > LPX_BATCH_LDS_BYTES ? alone : in_batch).push_back(k);
   }
   const double t_start = now_s();
-  for (int32_t k = 0; k < count; k++) {
-    memset(&results[k], 0, sizeof results[k]);
-    results[k].x0_slot = -1;
-    results[k].status = LPX_BAD_ARGUMENT;
-  }
+  init_results(results, count);
   double t_pivots = 0.0;
   const int32_t nb = (int32_t)in_batch.size();
-  const int64_t pw = (int64_t)n_max + m_max;
   if (nb > 0) {
-    std::vector<int32_t> bm(nb), bn(nb), bmax(nb), border, blen;
-    std::vector<double> bb((size_t)nb * m_max, 0.0), bc((size_t)nb * n_max, 0.0), bA;
-    const int64_t ldp = std::max(n_max, 1), strideP = (int64_t)m_max * ldp;
-    bA.assign((size_t)nb * strideP, 0.0);
-    if (o.restore_order) {
+    const Gathered G(F, in_batch, false);   // k_batch_solve negates c for `min` itself
+    std::vector<int32_t> bmax(nb), border, blen;
+    for (int32_t t = 0; t < nb; t++) bmax[t] = F.maximizes(in_batch[t]);
+    if (o.restore_order) {   // the one order for every phase-1 form, as lpx_solve_batch hands it to lpx_solve
       border.assign((size_t)nb * n_max, 0);
       blen.assign(nb, 0);
-    }
-    for (int32_t t = 0; t < nb; t++) {
-      const int32_t k = in_batch[t];
-      bm[t] = m ? m[k] : m_max;
-      bn[t] = n ? n[k] : n_max;
-      bmax[t] = !maximize || maximize[k] != 0;
-      for (int32_t i = 0; i < bm[t]; i++)
-        if (bn[t] > 0) memcpy(&bA[(size_t)t * strideP + (size_t)i * ldp], A + (int64_t)k * strideA + (int64_t)i * lda, (size_t)bn[t] * sizeof(double));
-      for (int32_t i = 0; i < bm[t]; i++) bb[(size_t)t * m_max + i] = b[(int64_t)k * m_max + i];
-      for (int32_t j = 0; j < bn[t]; j++) bc[(size_t)t * n_max + j] = c[(int64_t)k * n_max + j];
-      if (o.restore_order) {   // the one order for every phase-1 form, as lpx_solve_batch hands it to lpx_solve
-        blen[t] = std::min(o.restore_order_len < 0 ? bn[t] : o.restore_order_len, bn[t]);
+      for (int32_t t = 0; t < nb; t++) {
+        blen[t] = std::min(o.restore_order_len < 0 ? G.n[t] : o.restore_order_len, G.n[t]);
         std::copy(o.restore_order, o.restore_order + blen[t], border.begin() + (size_t)t * n_max);
       }
     }
     DeviceRestore keep_device;
     BatchGuard guard;
-    if (int rc = create_checked(nb, m_max, n_max, bm.data(), bn.data(), bA.data(), ldp, strideP, bb.data(), bc.data(), nullptr,
-                                nullptr, o.device, &guard.B))
-      return rc;
+    if (int rc = G.create(o, guard)) return rc;
     lpx_batch* B = guard.B;
-    B->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
-    B->pricing = o.pricing;
     std::vector<lpx_solve_result> res(nb);
     if (int rc = lpx_batch_solve(B, bmax.data(), o.max_pivots, o.restore_order ? border.data() : nullptr,
                                  o.restore_order ? blen.data() : nullptr, res.data()))
       return rc;
     t_pivots = res[0].seconds_pivots;
-    std::vector<double> bx;
-    std::vector<int32_t> bp;
-    if (x_out) bx.assign((size_t)nb * n_max, 0.0);
-    if (perm_out) bp.assign((size_t)nb * pw, 0);
-    if (int rc = lpx_batch_solutions(B, x_out ? bx.data() : nullptr, perm_out ? bp.data() : nullptr)) return rc;
+    std::vector<double> img;
+    if (x_out || perm_out)
+      if (int rc = read_images(B, img)) return rc;
     for (int32_t t = 0; t < nb; t++) {
-      const int32_t k = in_batch[t];
-      results[k] = res[t];
-      if (B->n_cur[t] != bn[t]) continue;   // as lpx_solve: only an m x n state is the caller's
-      if (perm_out && bn[t] + bm[t] > 0) memcpy(perm_out + k * pw, bp.data() + t * pw, ((size_t)bn[t] + bm[t]) * sizeof(int32_t));
-      if (x_out && bn[t] > 0) memcpy(x_out + (int64_t)k * n_max, bx.data() + (size_t)t * n_max, (size_t)bn[t] * sizeof(double));
+      results[in_batch[t]] = res[t];
+      if (x_out || perm_out) write_solution(B, img, t, in_batch[t], x_out, perm_out);   // as lpx_solve: only an m x n state
     }
   }
   if (n_in_batch) *n_in_batch = nb;
-  for (int32_t k : alone) {
-    lpx_solve_options oa = o;
-    oa.x_out = x_out ? x_out + (int64_t)k * n_max : nullptr;
-    oa.perm_out = perm_out ? perm_out + k * pw : nullptr;
-    const int rc = lpx_solve(m ? m[k] : m_max, n ? n[k] : n_max, A ? A + (int64_t)k * strideA : nullptr, lda,
-                             b ? b + (int64_t)k * m_max : nullptr, c ? c + (int64_t)k * n_max : nullptr,
-                             !maximize || maximize[k] != 0, &oa, &results[k]);
-    if (rc == LPX_DEVICE_ERROR || rc == LPX_BAD_ARGUMENT) return rc;
-    t_pivots += results[k].seconds_pivots;
-  }
-  const double t_total = now_s() - t_start;
-  for (int32_t k = 0; k < count; k++) {
-    results[k].seconds_total = t_total;
-    results[k].seconds_pivots = t_pivots;
-  }
+  if (int rc = solve_alone(F, alone, o, results, x_out, perm_out, t_pivots)) return rc;
+  stamp_seconds(results, count, t_start, t_pivots);
   return 0;
 }

@@ -49,6 +49,23 @@ struct BatchLp {
   int dantzig;
 };
 
+// the LP of layout L (m rows, n_cur columns now) in the workgroup's LDS, as thread tid of T sees it
+__device__ __forceinline__ BatchLp batch_lp(double* lds, const BatchLayout& L, int m, int n_cur, int tid, int T, int dantzig) {
+  BatchLp S;
+  S.A = lds;
+  S.b = lds + L.b;
+  S.c = lds + L.c;
+  S.vp = lds + L.v;
+  S.perm = (int32_t*)(lds + L.perm);
+  S.col = lds + L.col;
+  S.sh_e = (RatioRow*)(S.col + ((m + 1) & ~1));
+  S.sh_l = S.sh_e + 16;
+  S.ld = (int)L.ld; S.m = m; S.n = n_cur;
+  S.tid = tid; S.T = T; S.lane = tid & 63; S.wave = tid >> 6; S.nw = T >> 6;
+  S.dantzig = dantzig;
+  return S;
+}
+
 // getEntering() over the whole of c (LPState.java:274-285): one barrier
 __device__ __forceinline__ RatioRow batch_entering(const BatchLp& S) {
   RatioRow ent = rr_none();
@@ -164,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void k_batch_simplex(const BatchArgs a) {
   if (k >= a.count) return;
   const int m = a.m[k], n = a.n[k];
   const BatchLayout L = batch_layout(m, n);
-  const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = T >> 6;
+  const int tid = threadIdx.x, T = blockDim.x;
   if (L.lds_bytes > a.lds_bytes) {  // the host sized the launch from the same formula: never taken, and never out of bounds
     if (tid == 0) { a.status[k] = 7 /* LPX_DEVICE_ERROR */; a.pivots[k] = 0; }
     return;
@@ -173,18 +190,7 @@ __global__ __launch_bounds__(kThreads) void k_batch_simplex(const BatchArgs a) {
   const int nvec = (int)(L.image >> 1);
   for (int q = tid; q < nvec; q += T) ((d2*)batch_lds)[q] = ((const d2*)image)[q];
 
-  BatchLp S;
-  S.A = batch_lds;
-  S.b = batch_lds + L.b;
-  S.c = batch_lds + L.c;
-  S.vp = batch_lds + L.v;
-  S.perm = (int32_t*)(batch_lds + L.perm);
-  S.col = batch_lds + L.col;
-  S.sh_e = (RatioRow*)(S.col + ((m + 1) & ~1));
-  S.sh_l = S.sh_e + 16;
-  S.ld = (int)L.ld; S.m = m; S.n = n;
-  S.tid = tid; S.T = T; S.lane = lane; S.wave = wave; S.nw = nw;
-  S.dantzig = a.dantzig;
+  const BatchLp S = batch_lp(batch_lds, L, m, n, tid, T, a.dantzig);
   __syncthreads();
 
   int64_t pivots = 0;
@@ -266,18 +272,7 @@ __global__ __launch_bounds__(kThreads) void k_batch_solve(const BatchSolveArgs a
   }
   __syncthreads();   // the scratch has been read
 
-  BatchLp S;
-  S.A = batch_lds;
-  S.b = batch_lds + L.b;
-  S.c = batch_lds + L.c;
-  S.vp = batch_lds + L.v;
-  S.perm = (int32_t*)(batch_lds + L.perm);
-  S.col = batch_lds + L.col;
-  S.sh_e = (RatioRow*)(S.col + ((m + 1) & ~1));
-  S.sh_l = S.sh_e + 16;
-  S.ld = (int)L.ld; S.m = m; S.n = phase1 ? na : n;
-  S.tid = tid; S.T = T; S.lane = lane; S.wave = wave; S.nw = nw;
-  S.dantzig = a.dantzig;
+  BatchLp S = batch_lp(batch_lds, L, m, phase1 ? na : n, tid, T, a.dantzig);
 
   int status = 0;
   int64_t pivots1 = 0, pivots2 = 0;
@@ -419,53 +414,45 @@ __global__ __launch_bounds__(kThreads) void k_batch_solve(const BatchSolveArgs a
   }
 }
 
-template <int kThreads>
-static hipError_t batch_launch_t(const BatchArgs& a, hipStream_t s) {
+// Host side of both kernels.  K names a kernel template and its argument block; the workgroup size picks the
+// instantiation (64, 256, 1024) here and nowhere else.
+struct BatchSimplexKernel {
+  using Args = BatchArgs;
+  template <int kThreads> static const void* fn() { return (const void*)k_batch_simplex<kThreads>; }
+};
+struct BatchSolveKernel {
+  using Args = BatchSolveArgs;
+  template <int kThreads> static const void* fn() { return (const void*)k_batch_solve<kThreads>; }
+};
+
+template <typename K>
+static const void* batch_kernel(int threads) {
+  return threads <= 64 ? K::template fn<64>() : threads <= 256 ? K::template fn<256>() : K::template fn<1024>();
+}
+
+template <typename K>
+static hipError_t batch_launch(const typename K::Args& a, hipStream_t s) {
+  if (a.count <= 0) return hipSuccess;
+  const void* const kernel = batch_kernel<K>(a.threads);
   // more than 64 KiB of dynamic LDS has to be asked for per kernel; the launch itself reports what the runtime refuses
-  (void)hipFuncSetAttribute((const void*)k_batch_simplex<kThreads>, hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
+  (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
   (void)hipGetLastError();
-  hipLaunchKernelGGL(k_batch_simplex<kThreads>, dim3(a.count), dim3(a.threads), (size_t)a.lds_bytes, s, a);
+  void* params[] = {(void*)&a};
+  (void)hipLaunchKernel(kernel, dim3(a.count), dim3(a.threads), params, (size_t)a.lds_bytes, s);
   return hipGetLastError();
 }
 
-hipError_t launch_batch_simplex(const BatchArgs& a, hipStream_t s) {
-  if (a.count <= 0) return hipSuccess;
-  if (a.threads <= 64) return batch_launch_t<64>(a, s);
-  if (a.threads <= 256) return batch_launch_t<256>(a, s);
-  return batch_launch_t<1024>(a, s);
-}
-
-int batch_blocks_per_cu(int threads, int lds_bytes) {
+template <typename K>
+static int batch_occupancy(int threads, int lds_bytes) {
   int nb = 0;
-  hipError_t e;
-  if (threads <= 64) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_simplex<64>, threads, (size_t)lds_bytes);
-  else if (threads <= 256) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_simplex<256>, threads, (size_t)lds_bytes);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_simplex<1024>, threads, (size_t)lds_bytes);
-  if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, batch_kernel<K>(threads), threads, (size_t)lds_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
   return nb;
 }
 
-template <int kThreads>
-static hipError_t batch_solve_launch_t(const BatchSolveArgs& a, hipStream_t s) {
-  (void)hipFuncSetAttribute((const void*)k_batch_solve<kThreads>, hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(k_batch_solve<kThreads>, dim3(a.count), dim3(a.threads), (size_t)a.lds_bytes, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_batch_solve(const BatchSolveArgs& a, hipStream_t s) {
-  if (a.count <= 0) return hipSuccess;
-  if (a.threads <= 64) return batch_solve_launch_t<64>(a, s);
-  if (a.threads <= 256) return batch_solve_launch_t<256>(a, s);
-  return batch_solve_launch_t<1024>(a, s);
-}
-
-int batch_solve_blocks_per_cu(int threads, int lds_bytes) {
-  int nb = 0;
-  hipError_t e;
-  if (threads <= 64) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_solve<64>, threads, (size_t)lds_bytes);
-  else if (threads <= 256) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_solve<256>, threads, (size_t)lds_bytes);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_batch_solve<1024>, threads, (size_t)lds_bytes);
-  if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
-  return nb;
-}
+hipError_t launch_batch_simplex(const BatchArgs& a, hipStream_t s) { return batch_launch<BatchSimplexKernel>(a, s); }
+int batch_blocks_per_cu(int threads, int lds_bytes) { return batch_occupancy<BatchSimplexKernel>(threads, lds_bytes); }
+hipError_t launch_batch_solve(const BatchSolveArgs& a, hipStream_t s) { return batch_launch<BatchSolveKernel>(a, s); }
+int batch_solve_blocks_per_cu(int threads, int lds_bytes) { return batch_occupancy<BatchSolveKernel>(threads, lds_bytes); }

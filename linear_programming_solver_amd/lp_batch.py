@@ -50,6 +50,29 @@ def _ip(a):
     return a.ctypes.data_as(_lib.ip) if a.size else None
 
 
+def solve_packed(p, maximize, opts, with_solutions):
+    """One of the one-shot calls on the arrays `p` of pack_lps (at least one LP), `maximize` int32 per LP and a
+    SolveOptions: lpx_solve_batch, or with_solutions lpx_solve_batch_all (phase 1 in the kernel too, x and perm out).
+    Returns (results, x, perm, forms the batch kernel took); x[count, n_max] and perm[count, n_max + m_max] are None
+    without with_solutions, and a perm row stays -1 where the library wrote nothing: the final state is not m x n."""
+    L = _lib.lib()
+    cnt = p["count"]
+    res = (_lib.SolveResult * cnt)()
+    took = C.c_int32(0)
+    args = [cnt, p["m_max"], p["n_max"], _ip(p["m"]), _ip(p["n"]), _dp(p["A"]), p["lda"], p["strideA"], _dp(p["b"]),
+            _dp(p["c"]), _ip(maximize), C.byref(opts), res]
+    x = perm = None
+    if with_solutions:
+        x = np.zeros((cnt, max(p["n_max"], 1)))
+        perm = np.full((cnt, max(p["n_max"] + p["m_max"], 1)), -1, dtype=np.int32)
+        rc = L.lpx_solve_batch_all(*args, _dp(x), _ip(perm), C.byref(took))
+    else:
+        rc = L.lpx_solve_batch(*args, C.byref(took))
+    if rc:
+        raise_for_status(rc)
+    return res, x, perm, int(took.value)
+
+
 class LPBatch:
     def __init__(self, lps, device=0, options=None, pricing="reference"):
         """`lps`: list of (A, b, c[, v]).  options: {"fused": 0 | 1 | 2} (the only option of a batch); without it the
@@ -154,12 +177,7 @@ class LPBatch:
         rc = self._L.lpx_batch_solutions(self._h, x.ctypes.data_as(_lib.dp), perm.ctypes.data_as(_lib.ip))   # one read-back
         if rc:
             raise_for_status(rc)
-        infos = []
-        for k in range(cnt):
-            m, n = int(self.m[k]), int(self.n[k])
-            written = n + m == 0 or perm[k, 0] >= 0
-            infos.append(SolveInfo(res[k], perm[k, :n + m].copy() if written else None, x[k, :n].copy() if written else None))
-        return infos
+        return [SolveInfo.of_batch_row(res[k], int(self.m[k]), int(self.n[k]), perm[k], x[k]) for k in range(cnt)]
 
     def shape(self, k):
         """(m, n) of LP k now: n + 1 columns after a solve() that ended inside phase 1."""

@@ -29,6 +29,13 @@ class SolveInfo:
         self.perm = perm
         self.x = x
 
+    @classmethod
+    def of_batch_row(cls, res, m, n, perm_row=None, x_row=None):
+        """One LP of a batch.  The library writes an LP's perm and x only where its final state is m x n, into rows the
+        caller pre-filled with -1: a row still starting with -1 (or no rows at all) gives perm = x = None."""
+        written = perm_row is not None and (n + m == 0 or perm_row[0] >= 0)
+        return cls(res, perm_row[:n + m].copy() if written else None, x_row[:n].copy() if written else None)
+
 
 class LPSolver:
     def __init__(self, device=0, max_pivots=-1, pricing="reference", devices=None, fused=None):
@@ -51,6 +58,25 @@ class LPSolver:
     def _arith_options(self):
         return {} if self.fused is None else {"fused": int(self.fused)}
 
+    def _solve_options(self):
+        """lpx_solve_options from this solver's fields."""
+        opts = _lib.SolveOptions()
+        opts.device = self.device
+        opts.max_pivots = self.max_pivots
+        opts.pricing = self.pricing
+        opts.fused = 0 if self.fused is None else (1 if self.fused else -1)
+        return opts
+
+    @classmethod
+    def _needs_phase1(cls, form, nan_hides=False):
+        """LPSolver.java:119 by minInB's rule, as the library and the kernel apply it: a NaN in b is never the minimum.
+        nan_hides: the rule solve_batch(phase1="host") has always routed by, np.min(b) < 0 -- the same unless b holds a
+        NaN, which makes np.min NaN and the answer False."""
+        mib = cls.min_in_b(form.b)
+        if mib == -1:
+            return False
+        return bool((np.min(form.b) if nan_hides else form.b[mib]) < 0.0)
+
     def solve(self, st_form, restore_order=None):
         """LPSolver.solve(stForm).  Unlike the reference this never modifies `st_form` (the reference
         negates stForm.c in place for `min`, :86-89, and pivots inside stForm.A/b/c, :267)."""
@@ -59,12 +85,8 @@ class LPSolver:
         A = np.ascontiguousarray(st_form.A, dtype=np.float64)
         b = np.ascontiguousarray(st_form.b, dtype=np.float64)
         c = np.ascontiguousarray(st_form.c, dtype=np.float64)
-        opts = _lib.SolveOptions()
-        opts.device = self.device
+        opts = self._solve_options()
         opts.has_variable_names = 1 if st_form.has_variable_names() else 0
-        opts.max_pivots = self.max_pivots
-        opts.pricing = self.pricing
-        opts.fused = 0 if self.fused is None else (1 if self.fused else -1)
         order = None
         if restore_order is not None:
             order = np.ascontiguousarray(np.asarray(restore_order, dtype=np.int32))
@@ -107,77 +129,32 @@ class LPSolver:
         (lpx_batch_solve_lds_bytes); self.last_batch carries perm and x per form and self.last_batch_x the solutions."""
         if phase1 not in ("host", "kernel"):
             raise ValueError('phase1 is "host" or "kernel"')
-        if phase1 == "kernel":
-            return self._solve_batch_in_kernel(list(forms))
-        from .lp_batch import pack_lps
+        from .lp_batch import LPBatch, pack_lps, solve_packed
         L = _lib.lib()
+        in_kernel = phase1 == "kernel"
         forms = list(forms)
         infos, answers = [None] * len(forms), [None] * len(forms)
-        # a NAMED form that needs phase 1 substitutes in the key-set order of its own names (restoreInitialLP): solve()
-        packed_idx = []
-        for k, f in enumerate(forms):
-            if f.has_variable_names() and f.n > 0 and self.min_in_b(f.b) != -1 and np.min(f.b) < 0.0:
-                try:
-                    answers[k] = self.solve(f)
-                except Exception as exc:   # what solve() raises is this form's entry
-                    answers[k] = exc
-                infos[k] = self.last
-            else:
-                packed_idx.append(k)
-        in_kernel = C.c_int32(0)
-        if packed_idx:
-            p = pack_lps([(forms[k].A, forms[k].b, forms[k].c) for k in packed_idx])
-            maxi = np.array([1 if forms[k].maximize else 0 for k in packed_idx], dtype=np.int32)
-            opts = _lib.SolveOptions()
-            opts.device = self.device
-            opts.max_pivots = self.max_pivots
-            opts.pricing = self.pricing
-            opts.fused = 0 if self.fused is None else (1 if self.fused else -1)
-            opts.restore_order_len = -1
-            res = (_lib.SolveResult * len(packed_idx))()
-            rc = L.lpx_solve_batch(p["count"], p["m_max"], p["n_max"], p["m"].ctypes.data_as(_lib.ip),
-                                   p["n"].ctypes.data_as(_lib.ip), p["A"].ctypes.data_as(_lib.dp) if p["A"].size else None,
-                                   p["lda"], p["strideA"], p["b"].ctypes.data_as(_lib.dp) if p["b"].size else None,
-                                   p["c"].ctypes.data_as(_lib.dp) if p["c"].size else None, maxi.ctypes.data_as(_lib.ip),
-                                   C.byref(opts), res, C.byref(in_kernel))
-            if rc:
-                raise_for_status(rc)
-            for t, k in enumerate(packed_idx):
-                infos[k] = SolveInfo(res[t], None, None)
-                exc = exception_for_status(res[t].status)
-                answers[k] = Decimal(res[t].objective_text.decode()) if exc is None else exc
-        self.last_batch = infos
-        self.last_batch_in_kernel = int(in_kernel.value)
-        return answers
-
-    def _solve_batch_in_kernel(self, forms):
-        from .lp_batch import LPBatch, pack_lps
-        L = _lib.lib()
-        infos, answers = [None] * len(forms), [None] * len(forms)
-        in_kernel = 0
-
-        def needs_phase1(f):   # minInB's rule, as the library and the kernel apply it (a NaN is never the minimum)
-            mib = self.min_in_b(f.b)
-            return mib != -1 and f.b[mib] < 0.0
 
         def answer(info):
             exc = exception_for_status(info.status)
             return Decimal(info.objective_text) if exc is None else exc
 
+        # A NAMED form that needs phase 1 substitutes in the key-set order of its own names (restoreInitialLP), which the
+        # packed call with its one order cannot give it: solve(), or in the kernel LPBatch.solve where its auxiliary LP fits
         named, packed_idx = [], []
         for k, f in enumerate(forms):
-            if f.has_variable_names() and f.n > 0 and needs_phase1(f):
-                if L.lpx_batch_solve_lds_bytes(f.m, f.n) <= _lib.BATCH_LDS_BYTES:
-                    named.append(k)
-                else:                                   # the auxiliary LP does not fit a workgroup: solve()
-                    try:
-                        answers[k] = self.solve(f)
-                    except Exception as exc:
-                        answers[k] = exc
-                    infos[k] = self.last
-            else:
+            if not (f.has_variable_names() and f.n > 0 and self._needs_phase1(f, nan_hides=not in_kernel)):
                 packed_idx.append(k)
-        if named:   # each substitutes in the key-set order of its own names (restoreInitialLP)
+            elif in_kernel and L.lpx_batch_solve_lds_bytes(f.m, f.n) <= _lib.BATCH_LDS_BYTES:
+                named.append(k)
+            else:
+                try:
+                    answers[k] = self.solve(f)
+                except Exception as exc:   # what solve() raises is this form's entry
+                    answers[k] = exc
+                infos[k] = self.last
+        took = len(named)
+        if named:
             batch = LPBatch([(forms[k].A, forms[k].b, forms[k].c) for k in named], device=self.device,
                             options=self._arith_options(), pricing=self.pricing)
             try:
@@ -187,39 +164,21 @@ class LPSolver:
                 batch.close()
             for k, info in zip(named, got):
                 infos[k], answers[k] = info, answer(info)
-            in_kernel += len(named)
         if packed_idx:
             p = pack_lps([(forms[k].A, forms[k].b, forms[k].c) for k in packed_idx])
-            cnt, pw = p["count"], p["n_max"] + p["m_max"]
             maxi = np.array([1 if forms[k].maximize else 0 for k in packed_idx], dtype=np.int32)
-            opts = _lib.SolveOptions()
-            opts.device = self.device
-            opts.max_pivots = self.max_pivots
-            opts.pricing = self.pricing
-            opts.fused = 0 if self.fused is None else (1 if self.fused else -1)
+            opts = self._solve_options()
             opts.restore_order_len = -1
-            res = (_lib.SolveResult * cnt)()
-            x = np.zeros((cnt, max(p["n_max"], 1)))
-            perm = np.full((cnt, max(pw, 1)), -1, dtype=np.int32)   # -1 stays where the final state is not m x n
-            took = C.c_int32(0)
-            rc = L.lpx_solve_batch_all(cnt, p["m_max"], p["n_max"], p["m"].ctypes.data_as(_lib.ip),
-                                       p["n"].ctypes.data_as(_lib.ip), p["A"].ctypes.data_as(_lib.dp) if p["A"].size else None,
-                                       p["lda"], p["strideA"], p["b"].ctypes.data_as(_lib.dp) if p["b"].size else None,
-                                       p["c"].ctypes.data_as(_lib.dp) if p["c"].size else None, maxi.ctypes.data_as(_lib.ip),
-                                       C.byref(opts), res, x.ctypes.data_as(_lib.dp), perm.ctypes.data_as(_lib.ip),
-                                       C.byref(took))
-            if rc:
-                raise_for_status(rc)
+            res, x, perm, packed_took = solve_packed(p, maxi, opts, with_solutions=in_kernel)
             for t, k in enumerate(packed_idx):
-                m, n = int(p["m"][t]), int(p["n"][t])
-                written = n + m == 0 or perm[t, 0] >= 0
-                infos[k] = SolveInfo(res[t], perm[t, :n + m].copy() if written else None,
-                                     x[t, :n].copy() if written else None)
+                rows = (perm[t], x[t]) if in_kernel else (None, None)
+                infos[k] = SolveInfo.of_batch_row(res[t], int(p["m"][t]), int(p["n"][t]), *rows)
                 answers[k] = answer(infos[k])
-            in_kernel += int(took.value)
+            took += packed_took
         self.last_batch = infos
-        self.last_batch_in_kernel = in_kernel
-        self.last_batch_x = [info.x for info in infos]
+        self.last_batch_in_kernel = took
+        if in_kernel:
+            self.last_batch_x = [info.x for info in infos]
         return answers
 
     @staticmethod

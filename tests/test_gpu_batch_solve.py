@@ -373,3 +373,93 @@ def test_unlimited_budget(lps, oracle):
              dense_lp(5, 6, 3) + (True,), degenerate_lp() + (True,)]
     res = solve_and_compare(lps, oracle, cases, unlimited=True)
     assert res[0]["status"] == OPTIMAL and res[1]["status"] == INFEASIBLE
+
+
+# ------------------------------------------------------------------------------------ 9. the one-shot calls' index scatter
+SENTINEL_X, SENTINEL_PERM = -7.25, -77
+
+
+def scatter_cases():
+    """Seven forms whose routes interleave under the padding of the largest (m_max x n_max = 97 x 200), `max` and `min`
+    and b >= 0 and a negative b in alternation.  The seeds (the s of seed_of, or dense_lp's seed) were chosen with the oracle
+    on the CPU: the 5 x 7 form (s = 0) and the 97 x 200 form (s = 0) are feasible and reach phase 2, the second 3 x 2 form
+    is infeasible by construction; the test asserts all of that from the oracle's results.  97 x 200 is one row past what
+    lpx_batch_solve_lds_bytes admits: lpx_solve_batch_all leaves it to lpx_solve."""
+    return [dense_lp(3, 2, 11) + (True,),
+            feasible_phase1_lp(5, 7, 0) + (False,),
+            dense_lp(1, 1, 12) + (True,),
+            feasible_phase1_lp(97, 200, 0) + (False,),
+            (np.zeros((0, 3)), np.zeros(0), np.array([0.5, -1.0, 0.25]), True),
+            infeasible_lp(3, 2, 0) + (False,),
+            dense_lp(4, 9, 13) + (True,)]
+
+
+def one_shot(lps, arith, cases, budget, all_in_kernel, maximize_given=True):
+    """lpx_solve_batch or lpx_solve_batch_all through ctypes.  Returns (SolveInfos, n_in_batch, x, perm): x and perm are
+    the rows handed to lpx_solve_batch_all, pre-filled with the sentinels, and None for lpx_solve_batch."""
+    from linear_programming_solver_amd import _lib
+    from linear_programming_solver_amd.lp_solver import SolveInfo
+    L = _lib.lib()
+    p = lps.pack_lps([case[:3] for case in cases])
+    cnt = p["count"]
+    maxi = np.array([1 if case[3] else 0 for case in cases], dtype=np.int32)
+    opts = _lib.SolveOptions()
+    opts.max_pivots = budget
+    opts.fused = 1 if arith == "fused" else -1
+    opts.restore_order_len = -1
+    res = (_lib.SolveResult * cnt)()
+    took = C.c_int32(-1)
+    args = [cnt, p["m_max"], p["n_max"], p["m"].ctypes.data_as(_lib.ip), p["n"].ctypes.data_as(_lib.ip),
+            p["A"].ctypes.data_as(_lib.dp), p["lda"], p["strideA"], p["b"].ctypes.data_as(_lib.dp),
+            p["c"].ctypes.data_as(_lib.dp), maxi.ctypes.data_as(_lib.ip) if maximize_given else None, C.byref(opts), res]
+    x = perm = None
+    if all_in_kernel:
+        x = np.full((cnt, p["n_max"]), SENTINEL_X)
+        perm = np.full((cnt, p["n_max"] + p["m_max"]), SENTINEL_PERM, dtype=np.int32)
+        rc = L.lpx_solve_batch_all(*args, x.ctypes.data_as(_lib.dp), perm.ctypes.data_as(_lib.ip), C.byref(took))
+    else:
+        rc = L.lpx_solve_batch(*args, C.byref(took))
+    assert rc == 0, _lib.last_error()
+    return [SolveInfo(res[k], None, None) for k in range(cnt)], took.value, x, perm
+
+
+def test_one_shot_calls_scatter_interleaved_routes(lps, oracle, arith):
+    from linear_programming_solver_amd import _lib
+    L = _lib.lib()
+    cases = scatter_cases()
+    shapes = [(len(case[1]), len(case[2])) for case in cases]
+    assert shapes == [(3, 2), (5, 7), (1, 1), (97, 200), (0, 3), (3, 2), (4, 9)]
+    assert L.lpx_batch_solve_lds_bytes(96, 200) <= _lib.BATCH_LDS_BYTES < L.lpx_batch_solve_lds_bytes(97, 200)
+    assert [needs_phase1(case[1]) for case in cases] == [False, True, False, True, False, True, False]
+    assert [case[3] for case in cases] == [True, False, True, False, True, False, True]
+    for maximize_given in (True, False):   # NULL flags: every form maximises
+        asked = cases if maximize_given else [case[:3] + (True,) for case in cases]
+        want = [oracle_solve(oracle, case, "reference") for case in asked]
+        res = [r for r, _ in want]
+        assert res[1]["phase1_used"] and res[1]["status"] in (OPTIMAL, UNBOUNDED) and res[1]["pivots1"] >= 2
+        assert res[3]["phase1_used"] and res[3]["status"] in (OPTIMAL, UNBOUNDED) and res[3]["pivots2"] >= 1
+        assert res[5]["status"] == INFEASIBLE and res[5]["final_n"] == 3
+        budget = 2 * max(r["pivots1"] + r["pivots2"] for r in res) + 100
+        if maximize_given:   # lpx_solve_batch refuses NULL flags: tests/test_batch_host.py
+            infos, took, _, _ = one_shot(lps, arith, asked, budget, all_in_kernel=False)
+            assert took == 4
+            for k, info in enumerate(infos):
+                compare_info(info, res[k], "(lpx_solve_batch, form %d)" % k)
+        infos, took, x, perm = one_shot(lps, arith, asked, budget, all_in_kernel=True, maximize_given=maximize_given)
+        assert took == 6
+        for k, (info, (r, st)) in enumerate(zip(infos, want)):
+            what = "(lpx_solve_batch_all, maximize %s, form %d)" % ("given" if maximize_given else "NULL", k)
+            compare_info(info, r, what)
+            m, n = shapes[k]
+            if st.n == n:
+                _, b, _, _, want_perm = st.read()
+                want_x = np.zeros(n)
+                for i in range(m):
+                    if want_perm[n + i] < n:
+                        want_x[want_perm[n + i]] = b[i]
+                assert list(perm[k, :n + m]) == list(want_perm), "perm differs " + what
+                assert np.array_equal(bits(x[k, :n]), bits(want_x)), "x differs " + what
+            else:   # the auxiliary LP of a solve that ended inside phase 1: the caller's rows are left alone
+                n = m = 0
+            assert np.all(x[k, n:] == SENTINEL_X) and np.all(perm[k, n + m:] == SENTINEL_PERM), "padding written " + what
+            st.close()
