@@ -475,6 +475,47 @@ int lpx_solve_batch_all(int32_t count, int32_t m_max, int32_t n_max, const int32
                         const int32_t* maximize, const lpx_solve_options* opts, lpx_solve_result* results,
                         double* x_out, int32_t* perm_out, int32_t* n_in_batch);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scenario batches: ONE m x n constraint matrix, `count` scenarios (b, c, max | min) on it, ONE launch, one workgroup per
+ * scenario running the whole of LPSolver.solve as lpx_batch_solve does (phase 1 included, bit for bit the same results).
+ * The matrix goes to the device once, with the handle; a solve sends b and c as the dense arrays they are and brings
+ * back x, perm and the results: per scenario m + n doubles up and n doubles, n + m ints and a few scalars down.  No
+ * per-LP image is built, uploaded or read back, which is what bounds lpx_solve_batch_all on such a sweep.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct lpx_scenarios lpx_scenarios;
+/* The matrix A (m x n, row-major, leading dimension lda >= n; HOST array, copied) on `device`.  The shape must fit the
+ * batch kernel (lpx_batch_lds_bytes(m, n) <= LPX_BATCH_LDS_BYTES).  A negative dimension or device, lda < n, a NULL A where
+ * m, n > 0 or a shape that does not fit give LPX_BAD_ARGUMENT before any device call. */
+int lpx_scenarios_create(int32_t m, int32_t n, const double* A, int64_t lda, int device, lpx_scenarios** out);
+void lpx_scenarios_destroy(lpx_scenarios* s);
+/* LPX_OPT_FUSED only, as lpx_batch_set_option. */
+int lpx_scenarios_set_option(lpx_scenarios* s, int32_t key, int64_t value);
+/* Entering rule of every scenario, as lpx_batch_set_pricing. */
+int lpx_scenarios_set_pricing(lpx_scenarios* s, int32_t pricing);
+/* BigDecimal LPSolver.solve(LPStandardForm stForm) for `count` scenarios of the handle's matrix      LPSolver.java:78-246
+ * Scenario k reads b + k*ldb (m doubles) and c + k*ldc (n doubles); ldb is 0 (ONE b for every scenario) or >= m, ldc is 0
+ * or >= n.  maximize[count], NULL: every scenario is a maximisation.  max_pivots is the budget of each scenario's whole
+ * solve.  restore_order / restore_order_len: the ONE order of restoreInitialLP for every scenario that takes phase 1, with
+ * the semantics of lpx_solve_options (NULL: lpx_java_default_name_order(n); a length < 0: n entries).  results[count] is
+ * what lpx_solve fills for scenario k alone; the times are those of the whole call (seconds_pivots: the launch).
+ * x_out (may be NULL) is double[count * n], perm_out (may be NULL) int32[count * (n + m)]: scenario k's row is written
+ * only when its final state is m x n, as in lpx_solve_batch_all (a basic original variable takes b[row], every other 0).
+ * The handle may be solved any number of times, each call independent of the others; its device buffers grow to the
+ * largest count seen.  A scenario whose b needs phase 1 (minInB finds a negative entry) must also fit
+ * lpx_batch_solve_lds_bytes(m, n): otherwise LPX_BAD_ARGUMENT naming the scenario and the shape -- there is no one-by-one
+ * fallback.  A negative count, a pitch between 1 and the dimension - 1, NULL results, a NULL b or c where data is due or a
+ * bad order entry give LPX_BAD_ARGUMENT likewise, all before the first device call. */
+int lpx_scenarios_solve(lpx_scenarios* s, int32_t count, const double* b, int64_t ldb, const double* c, int64_t ldc,
+                        const int32_t* maximize, int64_t max_pivots, const int32_t* restore_order, int32_t restore_order_len,
+                        lpx_solve_result* results, double* x_out, int32_t* perm_out);
+/* lpx_scenarios_create, lpx_scenarios_solve, lpx_scenarios_destroy.  Honoured options: device, max_pivots, pricing, fused
+ * (0 = the library's choice by size = two roundings at these sizes) and restore_order / restore_order_len;
+ * opts->keep_state, opts->perm_out and opts->x_out must be NULL.  All argument checks of both steps come before the first
+ * device call. */
+int lpx_solve_scenarios(int32_t m, int32_t n, const double* A, int64_t lda, int32_t count, const double* b, int64_t ldb,
+                        const double* c, int64_t ldc, const int32_t* maximize, const lpx_solve_options* opts,
+                        lpx_solve_result* results, double* x_out, int32_t* perm_out);
+
 /* LPState restoreInitialLP(auxLP, initial, indexOfX0)                   LPSolver.java:200-246
  * In place on the auxiliary-LP handle (m x (n+1), as left by phase 1): drops x0's column, rebuilds c and v by
  * substitution in keySet() order (`order`, order_len <= n original-variable indices; NULL = default-name order of all n), renumbers

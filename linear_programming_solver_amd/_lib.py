@@ -165,6 +165,14 @@ SYMBOLS = [
     ("lpx_batch_solve", C.c_int, [C.c_void_p, ip, C.c_int64, ip, ip, C.POINTER(SolveResult)]),
     ("lpx_solve_batch_all", C.c_int, [C.c_int32, C.c_int32, C.c_int32, ip, ip, dp, C.c_int64, C.c_int64, dp, dp, ip,
                                       C.POINTER(SolveOptions), C.POINTER(SolveResult), dp, ip, ip]),
+    ("lpx_scenarios_create", C.c_int, [C.c_int32, C.c_int32, dp, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("lpx_scenarios_destroy", None, [C.c_void_p]),
+    ("lpx_scenarios_set_option", C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
+    ("lpx_scenarios_set_pricing", C.c_int, [C.c_void_p, C.c_int32]),
+    ("lpx_scenarios_solve", C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, dp, C.c_int64, ip, C.c_int64, ip, C.c_int32,
+                                      C.POINTER(SolveResult), dp, ip]),
+    ("lpx_solve_scenarios", C.c_int, [C.c_int32, C.c_int32, dp, C.c_int64, C.c_int32, dp, C.c_int64, dp, C.c_int64, ip,
+                                      C.POINTER(SolveOptions), C.POINTER(SolveResult), dp, ip]),
 ]
 
 _lib = None

@@ -1,5 +1,6 @@
 // Batched solve behind the C ABI (include/lpx.h): many small LPs in ONE launch, one workgroup per LP with the LP's whole
-// state in LDS (lpx_batch.inc: k_batch_simplex runs the loop, k_batch_solve the whole of LPSolver.solve with phase 1).
+// state in LDS (lpx_batch.inc: k_batch_simplex runs the loop, k_batch_solve the whole of LPSolver.solve with phase 1,
+// k_batch_scenarios the same for many (b, c) on one matrix: lpx_scenarios at the end of this file).
 // The handle keeps one HBM image per LP (lpxk::BatchLayout).  lpx_solve_batch and lpx_solve_batch_all are built from one
 // set of pieces (Forms, check_one_shot, Gathered, solve_alone, stamp_seconds).  Every argument is checked before the first
 // device call, so a bad call answers LPX_BAD_ARGUMENT on a machine without a GPU too.
@@ -232,14 +233,16 @@ int create_checked(const Forms& F, const double* v, const int32_t* perm, int dev
 
 // LPX_BATCH_THREADS (debugging aid of scripts/bench_batch.py, read at every loop call): workgroup size instead of the
 // by-size choice, rounded down to a multiple of 64 inside 64..1024
-int threads_in_effect(const lpx_batch* B, bool solve = false) {
+int threads_or_env(int by_size) {
   const char* e = getenv("LPX_BATCH_THREADS");
   if (e && *e) {
     const int t = atoi(e);
     if (t > 0) return std::max(64, std::min(1024, t / 64 * 64));
   }
-  return solve ? B->solve_threads : B->threads;
+  return by_size;
 }
+
+int threads_in_effect(const lpx_batch* B, bool solve = false) { return threads_or_env(solve ? B->solve_threads : B->threads); }
 
 // dynamic LDS of the k_batch_solve launch: per LP the auxiliary layout where phase 1 is due, else the plain one
 int64_t solve_launch_lds(const lpx_batch* B) {
@@ -723,5 +726,342 @@ extern "C" int lpx_solve_batch_all(int32_t count, int32_t m_max, int32_t n_max, 
   if (n_in_batch) *n_in_batch = nb;
   if (int rc = solve_alone(F, alone, o, results, x_out, perm_out, t_pivots)) return rc;
   stamp_seconds(results, count, t_start, t_pivots);
+  return 0;
+}
+
+// ---- scenario batches: ONE constraint matrix, many (b, c) -- k_batch_scenarios ---------------------------------------------
+// The handle keeps the matrix on the device at pitch n.  A solve uploads b and c as they are (a strided copy, no host
+// gather), a flag word per scenario and the one restore order; the kernel writes x, perm and seven scalars per scenario.
+// The per-scenario buffers grow to the largest count seen.
+struct lpx_scenarios {
+  int device = 0;
+  int32_t m = 0, n = 0;
+  int fused = 0, pricing = 0;
+  hipStream_t stream = nullptr;
+  double* d_A = nullptr;
+  int32_t cap = 0;   // scenarios the buffers below hold
+  double *d_b = nullptr, *d_c = nullptr, *d_sv = nullptr, *d_x = nullptr;
+  int32_t *d_flags = nullptr, *d_order = nullptr, *d_si32 = nullptr, *d_perm = nullptr;
+  int64_t* d_si64 = nullptr;
+};
+
+namespace {
+
+void free_scenario_buffers(lpx_scenarios* S) {
+  (void)hipFree(S->d_b);
+  (void)hipFree(S->d_c);
+  (void)hipFree(S->d_sv);
+  (void)hipFree(S->d_x);
+  (void)hipFree(S->d_flags);
+  (void)hipFree(S->d_si32);
+  (void)hipFree(S->d_perm);
+  (void)hipFree(S->d_si64);
+  S->d_b = S->d_c = S->d_sv = S->d_x = nullptr;
+  S->d_flags = S->d_si32 = S->d_perm = nullptr;
+  S->d_si64 = nullptr;
+  S->cap = 0;
+}
+
+void free_scenarios(lpx_scenarios* S) {
+  if (!S) return;
+  if (S->stream || S->d_A) {
+    (void)hipSetDevice(S->device);
+    free_scenario_buffers(S);
+    (void)hipFree(S->d_A);
+    (void)hipFree(S->d_order);
+    if (S->stream) (void)hipStreamDestroy(S->stream);
+  }
+  delete S;
+}
+
+struct ScenariosGuard {
+  lpx_scenarios* S = nullptr;
+  ~ScenariosGuard() { free_scenarios(S); }
+};
+
+// the shape and the matrix of a scenario batch
+int check_scenario_matrix(const char* who, int32_t m, int32_t n, const double* A, int64_t lda, int device) {
+  if (m < 0 || n < 0) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": negative dimension");
+  if (lda < n) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": lda < n");
+  if (m > 0 && n > 0 && !A) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL array where data is due (A)");
+  if (device < 0) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": negative device");
+  const int64_t need = lds_bytes_of(m, n);
+  if (need > LPX_BATCH_LDS_BYTES) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: the shape %d x %d needs %lld bytes of LDS, a workgroup has %d", who, m, n, (long long)need,
+             LPX_BATCH_LDS_BYTES);
+    return fail(LPX_BAD_ARGUMENT, msg);
+  }
+  return 0;
+}
+
+// the arguments of one solve on an m x n matrix; fills flags[count]: bit 0 = maximise, bit 1 = minInB (LPSolver.java:375-386,
+// the rule of Forms::phase1) finds a negative entry in the scenario's b.  *any_p1: some scenario needs the auxiliary LP.
+int check_scenario_solve(const char* who, int32_t m, int32_t n, int32_t count, const double* b, int64_t ldb, const double* c,
+                         int64_t ldc, const int32_t* maximize, const int32_t* order, int32_t order_len,
+                         const lpx_solve_result* results, std::vector<int32_t>& flags, bool* any_p1) {
+  if (count < 0) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": negative count");
+  if (ldb != 0 && ldb < m) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": ldb is neither 0 nor >= m");
+  if (ldc != 0 && ldc < n) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": ldc is neither 0 nor >= n");
+  if (count > 0 && !results) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": results is NULL");
+  if (count > 0 && ((m > 0 && !b) || (n > 0 && !c)))
+    return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL array where data is due (b or c)");
+  if (order)
+    if (int rc = check_order(who, 0, m, n, order, order_len)) return rc;
+  flags.assign((size_t)std::max(count, 0), 0);
+  *any_p1 = false;
+  const bool aux_fits = solve_lds_bytes_of(m, n) <= LPX_BATCH_LDS_BYTES;
+  for (int32_t k = 0; k < count; k++) {
+    const double* bk = b ? b + (int64_t)k * ldb : nullptr;
+    const Forms one{1, m, n, nullptr, nullptr, nullptr, 0, 0, bk, nullptr, nullptr};
+    const bool p1 = m > 0 && one.phase1(0);
+    if (p1 && !aux_fits) {
+      char msg[240];
+      snprintf(msg, sizeof msg, "%s: scenario %d of shape %d x %d needs phase 1 and with it %lld bytes of LDS, a workgroup has %d",
+               who, k, m, n, (long long)solve_lds_bytes_of(m, n), LPX_BATCH_LDS_BYTES);
+      return fail(LPX_BAD_ARGUMENT, msg);
+    }
+    *any_p1 |= p1;
+    flags[k] = (!maximize || maximize[k] != 0 ? 1 : 0) | (p1 ? 2 : 0);
+  }
+  return 0;
+}
+
+int scenarios_create_checked(int32_t m, int32_t n, const double* A, int64_t lda, int device, lpx_scenarios** out) {
+  ScenariosGuard guard;
+  lpx_scenarios* S = guard.S = new lpx_scenarios();
+  S->device = device;
+  S->m = m;
+  S->n = n;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc((void**)&S->d_A, std::max<size_t>((size_t)m * n, 1) * sizeof(double)));
+  HIP_TRY(hipMalloc((void**)&S->d_order, (size_t)std::max(n, 1) * sizeof(int32_t)));
+  if (m > 0 && n > 0) {
+    HIP_TRY(hipMemcpy2DAsync(S->d_A, (size_t)n * sizeof(double), A, (size_t)lda * sizeof(double), (size_t)n * sizeof(double),
+                             (size_t)m, hipMemcpyHostToDevice, S->stream));
+    HIP_TRY(hipStreamSynchronize(S->stream));   // the caller's A is free again
+  }
+  guard.S = nullptr;
+  *out = S;
+  return 0;
+}
+
+int scenarios_reserve(lpx_scenarios* S, int32_t count) {
+  if (count <= S->cap) return 0;
+  free_scenario_buffers(S);
+  const size_t cnt = (size_t)count, m = (size_t)S->m, n = (size_t)S->n;
+  HIP_TRY(hipMalloc((void**)&S->d_b, std::max<size_t>(cnt * m, 1) * sizeof(double)));
+  HIP_TRY(hipMalloc((void**)&S->d_c, std::max<size_t>(cnt * n, 1) * sizeof(double)));
+  HIP_TRY(hipMalloc((void**)&S->d_sv, cnt * sizeof(double)));
+  HIP_TRY(hipMalloc((void**)&S->d_x, std::max<size_t>(cnt * n, 1) * sizeof(double)));
+  HIP_TRY(hipMalloc((void**)&S->d_flags, cnt * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&S->d_si32, 4 * cnt * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&S->d_perm, std::max<size_t>(cnt * (n + m), 1) * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&S->d_si64, 2 * cnt * sizeof(int64_t)));
+  S->cap = count;
+  return 0;
+}
+
+// `rows` vectors of `len` doubles at the host pitch ld (0: one vector) to the device at pitch len (0 stays 0)
+int upload_vectors(lpx_scenarios* S, double* dst, const double* src, int64_t ld, int32_t len, int32_t rows) {
+  if (len == 0 || rows == 0) return 0;
+  const size_t w = (size_t)len * sizeof(double);
+  if (ld == 0) HIP_TRY(hipMemcpyAsync(dst, src, w, hipMemcpyHostToDevice, S->stream));
+  else if (ld == len) HIP_TRY(hipMemcpyAsync(dst, src, w * (size_t)rows, hipMemcpyHostToDevice, S->stream));
+  else HIP_TRY(hipMemcpy2DAsync(dst, w, src, (size_t)ld * sizeof(double), w, (size_t)rows, hipMemcpyHostToDevice, S->stream));
+  return 0;
+}
+
+// the checked core of lpx_scenarios_solve: flags and any_p1 from check_scenario_solve, count > 0
+int scenarios_solve_checked(const char* who, lpx_scenarios* S, int32_t count, const double* b, int64_t ldb, const double* c,
+                            int64_t ldc, const std::vector<int32_t>& flags, bool any_p1, int64_t max_pivots,
+                            const int32_t* restore_order, int32_t restore_order_len, lpx_solve_result* results, double* x_out,
+                            int32_t* perm_out) {
+  const double t_start = now_s();
+  const int32_t m = S->m, n = S->n;
+  std::vector<int32_t> order((size_t)std::max(n, 1), 0);
+  int32_t olen = n;
+  if (restore_order) {
+    olen = restore_order_len < 0 ? n : restore_order_len;
+    std::copy(restore_order, restore_order + olen, order.begin());
+  } else if (n > 0) {
+    lpx_java_default_name_order(n, order.data());
+  }
+  init_results(results, count);
+  HIP_TRY(hipSetDevice(S->device));
+  if (int rc = scenarios_reserve(S, count)) return rc;
+  const size_t cnt = (size_t)count;
+  if (int rc = upload_vectors(S, S->d_b, b, ldb, m, count)) return rc;
+  if (int rc = upload_vectors(S, S->d_c, c, ldc, n, count)) return rc;
+  HIP_TRY(hipMemcpyAsync(S->d_flags, flags.data(), cnt * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
+  if (olen > 0) HIP_TRY(hipMemcpyAsync(S->d_order, order.data(), (size_t)olen * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
+  lpxk::BatchScenarioArgs a{};
+  a.count = count;
+  a.m = m;
+  a.n = n;
+  a.A = S->d_A;
+  a.b = S->d_b;
+  a.c = S->d_c;
+  a.ldb = ldb == 0 ? 0 : m;
+  a.ldc = ldc == 0 ? 0 : n;
+  a.flags = S->d_flags;
+  a.order = S->d_order;
+  a.order_len = olen;
+  a.status = S->d_si32;
+  a.phase1_used = a.status + cnt;
+  a.x0_slot = a.status + 2 * cnt;
+  a.n_final = a.status + 3 * cnt;
+  a.pivots1 = S->d_si64;
+  a.pivots2 = a.pivots1 + cnt;
+  a.v = S->d_sv;
+  a.x_out = x_out ? S->d_x : nullptr;
+  a.perm_out = perm_out ? S->d_perm : nullptr;
+  a.max_pivots = max_pivots < 0 ? -1 : max_pivots;
+  a.dantzig = S->pricing == 1;
+  a.fused = S->fused;
+  a.lds_bytes = (int32_t)std::max<int64_t>(lpxk::kBatchScratchBytes, any_p1 ? solve_lds_bytes_of(m, n) : lds_bytes_of(m, n));
+  a.threads = threads_or_env(threads_of(m, n + (any_p1 ? 1 : 0)));
+  std::vector<int32_t> h_i32(4 * cnt);
+  std::vector<int64_t> h_i64(2 * cnt);
+  std::vector<double> h_v(cnt);
+  HIP_TRY(hipStreamSynchronize(S->stream));   // the uploads are through: seconds_pivots is the launch alone
+  const double t0 = now_s();
+  HIP_TRY(lpxk::launch_batch_scenarios(a, S->stream));
+  HIP_TRY(hipStreamSynchronize(S->stream));
+  const double t_pivots = now_s() - t0;
+  HIP_TRY(hipMemcpyAsync(h_i32.data(), S->d_si32, h_i32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+  HIP_TRY(hipMemcpyAsync(h_i64.data(), S->d_si64, h_i64.size() * sizeof(int64_t), hipMemcpyDeviceToHost, S->stream));
+  HIP_TRY(hipMemcpyAsync(h_v.data(), S->d_sv, h_v.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+  HIP_TRY(hipStreamSynchronize(S->stream));
+  bool device_error = false, all_mxn = true;
+  for (int32_t k = 0; k < count; k++) {
+    lpx_solve_result& r = results[k];
+    r.status = h_i32[k];
+    r.phase1_used = h_i32[cnt + k];
+    r.x0_slot = h_i32[2 * cnt + k];
+    r.pivots_phase1 = h_i64[k];
+    r.pivots_phase2 = h_i64[cnt + k];
+    fill_objective(r, h_v[k], (flags[k] & 1) != 0);
+    device_error |= r.status == LPX_DEVICE_ERROR;
+    all_mxn &= h_i32[3 * cnt + k] == n;
+  }
+  if (device_error) {
+    stamp_seconds(results, count, t_start, t_pivots);
+    return fail(LPX_DEVICE_ERROR, std::string(who) + ": the kernel and the host disagree about a scenario's layout");
+  }
+  // x and perm: the kernel wrote the rows of the scenarios that ended m x n and no others.  All of them (the usual
+  // case): one copy each into the caller's arrays; else through a host copy, row by row
+  const size_t xw = (size_t)n, pw = (size_t)n + m;
+  if (all_mxn) {
+    if (x_out && xw > 0) HIP_TRY(hipMemcpyAsync(x_out, S->d_x, cnt * xw * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    if (perm_out && pw > 0) HIP_TRY(hipMemcpyAsync(perm_out, S->d_perm, cnt * pw * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+    HIP_TRY(hipStreamSynchronize(S->stream));
+  } else {
+    std::vector<double> hx(x_out ? cnt * xw : 0);
+    std::vector<int32_t> hp(perm_out ? cnt * pw : 0);
+    if (!hx.empty()) HIP_TRY(hipMemcpyAsync(hx.data(), S->d_x, hx.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    if (!hp.empty()) HIP_TRY(hipMemcpyAsync(hp.data(), S->d_perm, hp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+    HIP_TRY(hipStreamSynchronize(S->stream));
+    for (int32_t k = 0; k < count; k++) {
+      if (h_i32[3 * cnt + k] != n) continue;
+      if (!hx.empty()) memcpy(x_out + k * xw, hx.data() + k * xw, xw * sizeof(double));
+      if (!hp.empty()) memcpy(perm_out + k * pw, hp.data() + k * pw, pw * sizeof(int32_t));
+    }
+  }
+  stamp_seconds(results, count, t_start, t_pivots);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int lpx_scenarios_create(int32_t m, int32_t n, const double* A, int64_t lda, int device, lpx_scenarios** out) {
+  if (!out) return fail(LPX_BAD_ARGUMENT, "lpx_scenarios_create: out is NULL");
+  *out = nullptr;
+  if (int rc = check_scenario_matrix("lpx_scenarios_create", m, n, A, lda, device)) return rc;
+  DeviceRestore keep_device;
+  return scenarios_create_checked(m, n, A, lda, device, out);
+}
+
+extern "C" void lpx_scenarios_destroy(lpx_scenarios* S) {
+  DeviceRestore keep_device;
+  free_scenarios(S);
+}
+
+extern "C" int lpx_scenarios_set_option(lpx_scenarios* S, int32_t key, int64_t value) {
+  if (!S) return fail(LPX_BAD_ARGUMENT, "lpx_scenarios_set_option: NULL handle");
+  if (key != LPX_OPT_FUSED || value < 0 || value > 2)
+    return fail(LPX_BAD_ARGUMENT, "lpx_scenarios_set_option: only LPX_OPT_FUSED (0, 1, 2) applies to a scenario batch");
+  S->fused = value == 1;   // 2 = by size: a shape that fits a workgroup is far below the switch, i.e. 0
+  return 0;
+}
+
+extern "C" int lpx_scenarios_set_pricing(lpx_scenarios* S, int32_t pricing) {
+  if (!S || (pricing != 0 && pricing != 1)) return fail(LPX_BAD_ARGUMENT, "lpx_scenarios_set_pricing: bad argument");
+  S->pricing = pricing;
+  return 0;
+}
+
+// LPSolver.solve (LPSolver.java:78) for `count` scenarios (b, c, max | min) of the handle's matrix in ONE launch of
+// k_batch_scenarios; the handle is as it was afterwards
+extern "C" int lpx_scenarios_solve(lpx_scenarios* S, int32_t count, const double* b, int64_t ldb, const double* c, int64_t ldc,
+                                   const int32_t* maximize, int64_t max_pivots, const int32_t* restore_order,
+                                   int32_t restore_order_len, lpx_solve_result* results, double* x_out, int32_t* perm_out) {
+  const char* who = "lpx_scenarios_solve";
+  if (!S) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL handle");
+  std::vector<int32_t> flags;
+  bool any_p1 = false;
+  if (int rc = check_scenario_solve(who, S->m, S->n, count, b, ldb, c, ldc, maximize, restore_order, restore_order_len, results,
+                                    flags, &any_p1))
+    return rc;
+  if (count == 0) return 0;
+  DeviceRestore keep_device;
+  return scenarios_solve_checked(who, S, count, b, ldb, c, ldc, flags, any_p1, max_pivots, restore_order, restore_order_len,
+                                 results, x_out, perm_out);
+}
+
+// create, solve, destroy
+extern "C" int lpx_solve_scenarios(int32_t m, int32_t n, const double* A, int64_t lda, int32_t count, const double* b,
+                                   int64_t ldb, const double* c, int64_t ldc, const int32_t* maximize,
+                                   const lpx_solve_options* opts, lpx_solve_result* results, double* x_out, int32_t* perm_out) {
+  const char* who = "lpx_solve_scenarios";
+  lpx_solve_options o{};
+  o.max_pivots = -1;
+  if (opts) o = *opts;
+  if (o.keep_state || o.perm_out || o.x_out)
+    return fail(LPX_BAD_ARGUMENT, std::string(who) + ": opts->keep_state, opts->perm_out and opts->x_out must be NULL");
+  if (o.pricing != 0 && o.pricing != 1) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": bad pricing");
+  if (int rc = check_scenario_matrix(who, m, n, A, lda, o.device)) return rc;
+  std::vector<int32_t> flags;
+  bool any_p1 = false;
+  if (int rc = check_scenario_solve(who, m, n, count, b, ldb, c, ldc, maximize, o.restore_order, o.restore_order_len, results,
+                                    flags, &any_p1))
+    return rc;
+  if (count == 0) return 0;
+  const double t_start = now_s();
+  DeviceRestore keep_device;
+  ScenariosGuard guard;
+  if (int rc = scenarios_create_checked(m, n, A, lda, o.device, &guard.S)) return rc;
+  guard.S->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
+  guard.S->pricing = o.pricing;
+  if (int rc = scenarios_solve_checked(who, guard.S, count, b, ldb, c, ldc, flags, any_p1, o.max_pivots, o.restore_order,
+                                       o.restore_order_len, results, x_out, perm_out))
+    return rc;
+  stamp_seconds(results, count, t_start, results[0].seconds_pivots);   // the times of the whole call, creation included
+  return 0;
+}
+
+// What the launch of lpx_scenarios_solve looks like for this handle (scripts/bench_scenarios.py): not part of include/lpx.h
+extern "C" int lpxi_scenarios_launch_info(lpx_scenarios* S, int32_t phase1, int32_t* threads, int32_t* lds_bytes,
+                                          int32_t* blocks_per_cu) {
+  if (!S) return fail(LPX_BAD_ARGUMENT, "lpxi_scenarios_launch_info: NULL handle");
+  DeviceRestore keep_device;
+  HIP_TRY(hipSetDevice(S->device));
+  const int t = threads_or_env(threads_of(S->m, S->n + (phase1 ? 1 : 0)));
+  const int lds = (int)std::min<int64_t>(std::max<int64_t>(lpxk::kBatchScratchBytes, phase1 ? solve_lds_bytes_of(S->m, S->n)
+                                                                                            : lds_bytes_of(S->m, S->n)), INT32_MAX);
+  if (threads) *threads = t;
+  if (lds_bytes) *lds_bytes = lds;
+  if (blocks_per_cu) *blocks_per_cu = lpxk::batch_scenarios_blocks_per_cu(t, lds);
   return 0;
 }

@@ -240,21 +240,134 @@ __device__ __forceinline__ void batch_wave_shift_left(V* row, int from, int len,
   }
 }
 
-template <int kThreads>
-__global__ __launch_bounds__(kThreads) void k_batch_solve(const BatchSolveArgs a) {
-  extern __shared__ __attribute__((aligned(16))) double batch_lds[];
-  const int k = blockIdx.x;
-  if (k >= a.count) return;
-  const int m = a.m[k], n = a.n[k], na = n + 1;
+// The two ends of a solve: where an LP's entries come from and where its result goes.  batch_solve_body below runs
+// everything between them and asks its `Ends` for
+//   b_at(i), maximize(), host_phase1(), order(), order_len()     what minInB, the guards and the restore read
+//   load(S, maximize)                 the slack form (convertIntoSlackForm :248-272) into S, c negated for `min`; ends
+//                                     behind a barrier
+//   load_aux(S, c0, maximize)         A at the auxiliary pitch with column n = -1, b, and c0 = c negated for `min`
+//   store(S) / store_restored(S)      the final m x n state: S in the plain layout / at the auxiliary pitch
+//   store_aux(S, L)                   the m x (n + 1) auxiliary LP of a solve that ended inside phase 1
+// and writes the seven per-LP scalars through the fields every argument block has under the same names.
+//
+// BatchImageEnds (k_batch_solve): one HBM image per LP (BatchLayout), read whole and written back whole.
+struct BatchImageEnds {
+  const BatchSolveArgs& a;
+  const int k, m, n;
+  double* const image;
+  const BatchLayout L0;
+  __device__ __forceinline__ BatchImageEnds(const BatchSolveArgs& a_, int k_, int m_, int n_)
+      : a(a_), k(k_), m(m_), n(n_), image(a_.image + a_.offset[k_]), L0(batch_layout(m_, n_)) {}
+  __device__ __forceinline__ double b_at(int i) const { return image[L0.b + i]; }
+  __device__ __forceinline__ bool maximize() const { return a.maximize == nullptr || a.maximize[k] != 0; }
+  __device__ __forceinline__ bool host_phase1() const { return a.phase1[k] != 0; }
+  __device__ __forceinline__ const int32_t* order() const { return a.order + (int64_t)k * a.order_pitch; }
+  __device__ __forceinline__ int order_len() const { return a.order_len[k]; }
+  __device__ __forceinline__ void load(const BatchLp& S, bool maximize) const {
+    const int nvec = (int)(L0.image >> 1);
+    for (int q = S.tid; q < nvec; q += S.T) ((d2*)S.A)[q] = ((const d2*)image)[q];
+    __syncthreads();
+    if (!maximize)
+      for (int j = S.tid; j < n; j += S.T) S.c[j] = -S.c[j];                        // :86-89
+    __syncthreads();
+  }
+  __device__ __forceinline__ void load_aux(const BatchLp& S, double* c0, bool maximize) const {
+    const int ld0 = (int)L0.ld, ld = S.ld;
+    for (int i = S.wave; i < m; i += S.nw) {
+      for (int j = S.lane; j < n; j += 64) S.A[i * ld + j] = image[(int64_t)i * ld0 + j];
+      if (S.lane == 0) S.A[i * ld + n] = -1.0;                                      // :293
+    }
+    for (int i = S.tid; i < m; i += S.T) S.b[i] = image[L0.b + i];
+    for (int j = S.tid; j < n; j += S.T) {
+      const double cj = image[L0.c + j];
+      c0[j] = maximize ? cj : -cj;                                                  // :86-89
+    }
+  }
+  __device__ __forceinline__ void store(const BatchLp& S) const {
+    const int nvec = (int)(L0.image >> 1);
+    for (int q = S.tid; q < nvec; q += S.T) ((d2*)image)[q] = ((const d2*)S.A)[q];
+  }
+  // the front of the LDS IS the image of the m x (n + 1) auxiliary LP
+  __device__ __forceinline__ void store_aux(const BatchLp& S, const BatchLayout& L) const {
+    const int nvec = (int)(L.image >> 1);
+    for (int q = S.tid; q < nvec; q += S.T) ((d2*)image)[q] = ((const d2*)S.A)[q];
+  }
+  // m x n at the auxiliary pitch: entry by entry into batch_layout(m, n)
+  __device__ __forceinline__ void store_restored(const BatchLp& S) const {
+    const int ld0 = (int)L0.ld, ld = S.ld;
+    for (int i = S.wave; i < m; i += S.nw)
+      for (int j = S.lane; j < n; j += 64) image[(int64_t)i * ld0 + j] = S.A[i * ld + j];
+    for (int i = S.tid; i < m; i += S.T) image[L0.b + i] = S.b[i];
+    for (int j = S.tid; j < n; j += S.T) image[L0.c + j] = S.c[j];
+    if (S.tid == 0) image[L0.v] = *S.vp;
+    int32_t* const g_perm = (int32_t*)(image + L0.perm);
+    for (int s = S.tid; s < n + m; s += S.T) g_perm[s] = S.perm[s];
+  }
+};
+
+// BatchScenarioEnds (k_batch_scenarios): ONE m x n matrix in HBM (row-major at pitch n) for every workgroup, scenario k's
+// b at b + k * ldb and c at c + k * ldc (a pitch of 0: one vector for all), bit 0 of flags[k] = maximise, bit 1 = the host's
+// minInB verdict; v = 0 and the identity permutation are made on chip.  No image goes back: an m x n final state leaves
+// its perm and its solution, straight from LDS -- perm is a permutation, so every original id < n sits in exactly one
+// slot and every x[id] is written exactly once (0 from a nonbasic slot, b[row] from a basic row); the auxiliary LP of a
+// solve that ended inside phase 1 leaves nothing.
+struct BatchScenarioEnds {
+  const BatchScenarioArgs& a;
+  const int k, m, n;
+  const double *const gb, *const gc;
+  const int32_t flags;
+  __device__ __forceinline__ BatchScenarioEnds(const BatchScenarioArgs& a_, int k_)
+      : a(a_), k(k_), m(a_.m), n(a_.n), gb(a_.b + (int64_t)k_ * a_.ldb), gc(a_.c + (int64_t)k_ * a_.ldc), flags(a_.flags[k_]) {}
+  __device__ __forceinline__ double b_at(int i) const { return gb[i]; }
+  __device__ __forceinline__ bool maximize() const { return (flags & 1) != 0; }
+  __device__ __forceinline__ bool host_phase1() const { return (flags & 2) != 0; }
+  __device__ __forceinline__ const int32_t* order() const { return a.order; }
+  __device__ __forceinline__ int order_len() const { return a.order_len; }
+  // one wave per row, 8-byte accesses: the rows of the shared matrix at pitch n into the odd pitch of S
+  __device__ __forceinline__ void load_rows(const BatchLp& S) const {
+    const int ld = S.ld;
+    for (int i = S.wave; i < m; i += S.nw)
+      for (int j = S.lane; j < n; j += 64) S.A[i * ld + j] = a.A[(int64_t)i * n + j];
+    for (int i = S.tid; i < m; i += S.T) S.b[i] = gb[i];
+  }
+  __device__ __forceinline__ void load(const BatchLp& S, bool maximize) const {
+    load_rows(S);
+    for (int j = S.tid; j < n; j += S.T) S.c[j] = maximize ? gc[j] : -gc[j];        // :86-89
+    if (S.tid == 0) *S.vp = 0.0;
+    for (int s = S.tid; s < n + m; s += S.T) S.perm[s] = s;
+    __syncthreads();
+  }
+  __device__ __forceinline__ void load_aux(const BatchLp& S, double* c0, bool maximize) const {
+    load_rows(S);
+    for (int i = S.tid; i < m; i += S.T) S.A[i * S.ld + n] = -1.0;                  // :293
+    for (int j = S.tid; j < n; j += S.T) c0[j] = maximize ? gc[j] : -gc[j];         // :86-89
+  }
+  __device__ __forceinline__ void store(const BatchLp& S) const {
+    int32_t* const g_perm = a.perm_out ? a.perm_out + (int64_t)k * (n + m) : nullptr;
+    double* const g_x = a.x_out ? a.x_out + (int64_t)k * n : nullptr;
+    for (int s = S.tid; s < n + m; s += S.T) {
+      const int32_t id = S.perm[s];
+      if (g_perm) g_perm[s] = id;
+      if (g_x && id >= 0 && id < n) g_x[id] = s < n ? 0.0 : S.b[s - n];
+    }
+  }
+  __device__ __forceinline__ void store_aux(const BatchLp&, const BatchLayout&) const {}
+  __device__ __forceinline__ void store_restored(const BatchLp& S) const { store(S); }
+};
+
+// LPSolver.solve (LPSolver.java:78-133) for the m x n form behind `io`, by the whole workgroup in its LDS
+template <typename Ends>
+__device__ __forceinline__ void batch_solve_body(double* batch_lds, const Ends& io, const int m, const int n) {
+  const auto& a = io.a;
+  const int k = io.k, na = n + 1;
   const BatchLayout L0 = batch_layout(m, n);
   const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = T >> 6;
-  double* const image = a.image + a.offset[k];
-  const bool maximize = a.maximize == nullptr || a.maximize[k] != 0;
+  const bool maximize = io.maximize();
 
-  // minInB straight from the HBM image; the front of the LDS (every launch has at least kBatchScratchBytes) is the scratch
+  // minInB straight from HBM; the front of the LDS (every launch has at least kBatchScratchBytes) is the scratch
   RatioRow mb = rr_none();
   for (int i = tid; i < m; i += T) {
-    const double bi = image[L0.b + i];
+    const double bi = io.b_at(i);
     if (bi < kInf) mb = rr_min(mb, RatioRow{bi, i, 0});
   }
   mb = batch_reduce(mb, (RatioRow*)batch_lds, lane, wave, nw);
@@ -262,8 +375,8 @@ __global__ __launch_bounds__(kThreads) void k_batch_solve(const BatchSolveArgs a
   const bool phase1 = mib != INT_MAX && mb.ratio < 0.0;                             // LPSolver.java:119
   const BatchSolveLayout W = batch_solve_layout(m, n);
   const BatchLayout L = phase1 ? W.aux : L0;
-  // the host sized the launch and the image room with the same rule from the same b: never taken, and never out of bounds
-  if ((phase1 ? W.lds_bytes : L0.lds_bytes) > a.lds_bytes || phase1 != (a.phase1[k] != 0)) {
+  // the host sized the launch and its buffers with the same rule from the same b: never taken, and never out of bounds
+  if ((phase1 ? W.lds_bytes : L0.lds_bytes) > a.lds_bytes || phase1 != io.host_phase1()) {
     if (tid == 0) {
       a.status[k] = 7 /* LPX_DEVICE_ERROR */;
       a.phase1_used[k] = 0; a.x0_slot[k] = -1; a.n_final[k] = n; a.pivots1[k] = 0; a.pivots2[k] = 0; a.v[k] = 0.0;
@@ -278,32 +391,20 @@ __global__ __launch_bounds__(kThreads) void k_batch_solve(const BatchSolveArgs a
   int64_t pivots1 = 0, pivots2 = 0;
   int x0 = -1, n_final = n, none = -1;
   if (!phase1) {
-    // convertIntoSlackForm (:248-272): the image as it is, c negated for `min`
-    const int nvec = (int)(L0.image >> 1);
-    for (int q = tid; q < nvec; q += T) ((d2*)batch_lds)[q] = ((const d2*)image)[q];
-    __syncthreads();
-    if (!maximize)
-      for (int j = tid; j < n; j += T) S.c[j] = -S.c[j];                            // :86-89
-    __syncthreads();
+    io.load(S, maximize);                                                           // convertIntoSlackForm (:248-272)
     status = batch_loop(S, batch_entering(S), a.max_pivots, pivots2, none);         // :96-114
     __syncthreads();
-    for (int q = tid; q < nvec; q += T) ((d2*)image)[q] = ((const d2*)batch_lds)[q];
+    io.store(S);
   } else {
     double* const c0 = batch_lds + W.c0;
     int32_t* const order = (int32_t*)(batch_lds + W.order);
     int32_t* const slot_of = (int32_t*)(batch_lds + W.slot);
-    const int n_ord = a.order_len[k];
-    const int32_t* const g_order = a.order + (int64_t)k * a.order_pitch;
-    const int ld0 = (int)L0.ld, ld = S.ld;
+    const int n_ord = io.order_len();
+    const int32_t* const g_order = io.order();
+    const int ld = S.ld;
     // convertIntoAuxLP (:283-321)
-    for (int i = wave; i < m; i += nw) {
-      for (int j = lane; j < n; j += 64) S.A[i * ld + j] = image[(int64_t)i * ld0 + j];
-      if (lane == 0) S.A[i * ld + n] = -1.0;                                        // :293
-    }
-    for (int i = tid; i < m; i += T) S.b[i] = image[L0.b + i];
+    io.load_aux(S, c0, maximize);
     for (int j = tid; j < n; j += T) {
-      const double cj = image[L0.c + j];
-      c0[j] = maximize ? cj : -cj;                                                  // :86-89
       S.c[j] = 0.0;                                                                 // :299-301
       if (j < n_ord) order[j] = g_order[j];
     }
@@ -390,18 +491,8 @@ __global__ __launch_bounds__(kThreads) void k_batch_solve(const BatchSolveArgs a
       status = batch_loop(S, batch_entering(S), lim2, pivots2, none);               // :96-114
       __syncthreads();
     }
-    if (n_final == na) {   // ended inside phase 1: the front of the LDS IS the image of the m x (n + 1) auxiliary LP
-      const int nvec = (int)(L.image >> 1);
-      for (int q = tid; q < nvec; q += T) ((d2*)image)[q] = ((const d2*)batch_lds)[q];
-    } else {               // m x n at the auxiliary pitch: entry by entry into batch_layout(m, n)
-      for (int i = wave; i < m; i += nw)
-        for (int j = lane; j < n; j += 64) image[(int64_t)i * ld0 + j] = S.A[i * ld + j];
-      for (int i = tid; i < m; i += T) image[L0.b + i] = S.b[i];
-      for (int j = tid; j < n; j += T) image[L0.c + j] = S.c[j];
-      if (tid == 0) image[L0.v] = *S.vp;
-      int32_t* const g_perm = (int32_t*)(image + L0.perm);
-      for (int s = tid; s < n + m; s += T) g_perm[s] = S.perm[s];
-    }
+    if (n_final == na) io.store_aux(S, L);   // ended inside phase 1
+    else io.store_restored(S);
   }
   if (tid == 0) {
     a.status[k] = status;
@@ -414,7 +505,26 @@ __global__ __launch_bounds__(kThreads) void k_batch_solve(const BatchSolveArgs a
   }
 }
 
-// Host side of both kernels.  K names a kernel template and its argument block; the workgroup size picks the
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void k_batch_solve(const BatchSolveArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double batch_lds[];
+  const int k = blockIdx.x;
+  if (k >= a.count) return;
+  const int m = a.m[k], n = a.n[k];
+  batch_solve_body(batch_lds, BatchImageEnds(a, k, m, n), m, n);
+}
+
+// k_batch_scenarios: k_batch_solve for `count` scenarios of ONE m x n constraint matrix, one workgroup per scenario
+// (BatchScenarioEnds above: only b, c and a flag word per scenario come up from HBM, only perm, x and seven scalars go down).
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void k_batch_scenarios(const BatchScenarioArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double batch_lds[];
+  const int k = blockIdx.x;
+  if (k >= a.count) return;
+  batch_solve_body(batch_lds, BatchScenarioEnds(a, k), a.m, a.n);
+}
+
+// Host side of the three kernels.  K names a kernel template and its argument block; the workgroup size picks the
 // instantiation (64, 256, 1024) here and nowhere else.
 struct BatchSimplexKernel {
   using Args = BatchArgs;
@@ -423,6 +533,10 @@ struct BatchSimplexKernel {
 struct BatchSolveKernel {
   using Args = BatchSolveArgs;
   template <int kThreads> static const void* fn() { return (const void*)k_batch_solve<kThreads>; }
+};
+struct BatchScenarioKernel {
+  using Args = BatchScenarioArgs;
+  template <int kThreads> static const void* fn() { return (const void*)k_batch_scenarios<kThreads>; }
 };
 
 template <typename K>
@@ -456,3 +570,5 @@ hipError_t launch_batch_simplex(const BatchArgs& a, hipStream_t s) { return batc
 int batch_blocks_per_cu(int threads, int lds_bytes) { return batch_occupancy<BatchSimplexKernel>(threads, lds_bytes); }
 hipError_t launch_batch_solve(const BatchSolveArgs& a, hipStream_t s) { return batch_launch<BatchSolveKernel>(a, s); }
 int batch_solve_blocks_per_cu(int threads, int lds_bytes) { return batch_occupancy<BatchSolveKernel>(threads, lds_bytes); }
+hipError_t launch_batch_scenarios(const BatchScenarioArgs& a, hipStream_t s) { return batch_launch<BatchScenarioKernel>(a, s); }
+int batch_scenarios_blocks_per_cu(int threads, int lds_bytes) { return batch_occupancy<BatchScenarioKernel>(threads, lds_bytes); }

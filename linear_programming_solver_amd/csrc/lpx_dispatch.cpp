@@ -94,6 +94,12 @@ hipError_t launch_batch_solve(const BatchSolveArgs& a, hipStream_t s) {
 int batch_solve_blocks_per_cu(int threads, int lds_bytes) {
   return std::min(plain::batch_solve_blocks_per_cu(threads, lds_bytes), fused::batch_solve_blocks_per_cu(threads, lds_bytes));
 }
+hipError_t launch_batch_scenarios(const BatchScenarioArgs& a, hipStream_t s) {
+  return a.fused ? fused::launch_batch_scenarios(a, s) : plain::launch_batch_scenarios(a, s);
+}
+int batch_scenarios_blocks_per_cu(int threads, int lds_bytes) {
+  return std::min(plain::batch_scenarios_blocks_per_cu(threads, lds_bytes), fused::batch_scenarios_blocks_per_cu(threads, lds_bytes));
+}
 void launch_transpose(const double* dA, int64_t lda, double* dAt, int64_t ldat, int m, int n, hipStream_t s) {
   plain::launch_transpose(dA, lda, dAt, ldat, m, n, s);
 }

@@ -200,6 +200,34 @@ struct BatchSolveArgs {
   int32_t lds_bytes;
   int32_t threads;
 };
+// k_batch_scenarios (k_batch_solve for `count` scenarios of ONE constraint matrix): the matrix once, b and c as dense
+// arrays, and no image in either direction.  The output fields carry the names they have in BatchSolveArgs: one body
+// (batch_solve_body, lpx_batch.inc) writes both.
+struct BatchScenarioArgs {
+  int32_t count;
+  int32_t m, n;              // every scenario's shape
+  const double* A;           // m x n, row-major at pitch n: shared by every workgroup
+  const double* b;           // scenario k's b[m] at b + k * ldb
+  const double* c;           // scenario k's c[n] at c + k * ldc
+  int64_t ldb, ldc;          // 0: one vector for every scenario
+  const int32_t* flags;      // [count] bit 0: maximise; bit 1: the host's minInB found a negative b (it sized the LDS from it)
+  const int32_t* order;      // [order_len] the ONE restore order (original-variable indices)
+  int32_t order_len;         // <= n
+  int32_t* status;           // [count] out: lpx_status
+  int32_t* phase1_used;      // [count] out
+  int32_t* x0_slot;          // [count] out: -1 without phase 1
+  int32_t* n_final;          // [count] out: n, or n + 1 when the solve ended inside phase 1
+  int64_t* pivots1;          // [count] out
+  int64_t* pivots2;          // [count] out
+  double* v;                 // [count] out: the objective constant of the final state
+  double* x_out;             // [count * n] or NULL; row k written only when n_final[k] == n
+  int32_t* perm_out;         // [count * (n + m)] or NULL; likewise
+  int64_t max_pivots;        // budget of the whole solve per scenario; < 0: unlimited
+  int32_t dantzig;
+  int32_t fused;
+  int32_t lds_bytes;
+  int32_t threads;
+};
 
 // ---- launch wrappers --------------------------------------------------------------------------------------------
 // lpx_kernels.hip is compiled twice: plain (one rounding per reference operation) and fused (updates as one FMA).

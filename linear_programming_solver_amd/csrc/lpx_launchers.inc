@@ -76,4 +76,7 @@ int batch_blocks_per_cu(int threads, int lds_bytes);
 // batched solve with phase 1 on chip: LPSolver.solve for a.count LPs in one launch (k_batch_solve, lpx_batch.inc)
 hipError_t launch_batch_solve(const BatchSolveArgs& a, hipStream_t s);
 int batch_solve_blocks_per_cu(int threads, int lds_bytes);
+// the same for a.count scenarios of one constraint matrix (k_batch_scenarios, lpx_batch.inc)
+hipError_t launch_batch_scenarios(const BatchScenarioArgs& a, hipStream_t s);
+int batch_scenarios_blocks_per_cu(int threads, int lds_bytes);
 void launch_transpose(const double* dA, int64_t lda, double* dAt, int64_t ldat, int m, int n, hipStream_t s);

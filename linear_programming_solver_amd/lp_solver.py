@@ -181,6 +181,28 @@ class LPSolver:
             self.last_batch_x = [info.x for info in infos]
         return answers
 
+    def solve_scenarios(self, A, b, c, maximize=None, restore_order=None):
+        """LPSolver.solve for many scenarios of ONE constraint matrix (LPScenarios): b of
+        shape (m,) or (count, m), c of shape (n,) or (count, n), maximize one flag per scenario (None: all maximise),
+        restore_order the one order of restoreInitialLP (None: the default-name order).  Every scenario, phase 1 included,
+        runs in ONE launch of the batch kernel.  Returns one entry per scenario exactly as solve_batch does: the Decimal
+        solve() would return or the exception INSTANCE it would raise.  self.last_batch holds a SolveInfo per scenario,
+        self.last_batch_x the solutions (None where the final state is not m x n).  Single device only."""
+        from .lp_scenarios import LPScenarios
+        sc = LPScenarios(A, device=self.device, options=self._arith_options(), pricing=self.pricing)
+        try:
+            infos = sc.solve(b, c, maximize=maximize, max_pivots=self.max_pivots, restore_order=restore_order)
+        finally:
+            sc.close()
+        answers = []
+        for info in infos:
+            exc = exception_for_status(info.status)
+            answers.append(Decimal(info.objective_text) if exc is None else exc)
+        self.last_batch = infos
+        self.last_batch_in_kernel = len(infos)
+        self.last_batch_x = [info.x for info in infos]
+        return answers
+
     @staticmethod
     def _key_set_order(form):
         """Iteration order of `initial.coefficients.keySet()` in restoreInitialLP (LPSolver.java:213-217) as
