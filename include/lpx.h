@@ -124,7 +124,7 @@ int lpx_pivot(lpx_state* s, int32_t entering, int32_t leaving);
  * only supply the initial values (debugging aid for the scripts/ helpers).  Setting an option between two loops
  * is allowed; inside a loop nothing reads them.  Unknown key / value out of range -> LPX_BAD_ARGUMENT. */
 typedef enum lpx_option {
-  LPX_OPT_BLOCK = 0,          /* pivots per sweep: 0 = by size (1 below ~18 MiB of tableau on a handle without a ring, 16 up to ~28 MiB, 32 up to ~7 GiB, 64 above; fused arithmetic: 64 from ~0.85 GiB), 1 = off, 2..64 (same as lpx_state_set_block) */
+  LPX_OPT_BLOCK = 0,          /* pivots per sweep: 0 = by size (1 below ~18 MiB of tableau on a handle without a ring, 16 up to ~28 MiB, 32 up to ~7 GiB, 64 above; fused arithmetic: 64 from ~0.85 GiB and, in a loop call with an unlimited budget or one of at least 256 pivots, 128 from 4 GiB on whole 512-column strips), 1 = off, 2..128 (same as lpx_state_set_block; blocks of 65..128 on one device only) */
   LPX_OPT_CHAIN = 1,          /* 1 = all decisions of a block in one persistent launch (default); 0 = three launches */
   LPX_OPT_OVERLAP = 2,        /* 1 = decisions of block k+1 beside the sweep of block k (default); 0 = serial        */
   LPX_OPT_OVERLAP_SERIAL = 3, /* 1 = the overlapped loop's kernels and buffers without concurrency (diagnostics)     */
@@ -153,7 +153,7 @@ int lpx_state_get_option(const lpx_state* s, int32_t key, int64_t* value);
 /* What the handle actually did (the by-size choices, and whether the placement assumptions of the blocked loop
  * held on this runtime); filled from the last lpx_simplex_loop. */
 typedef struct lpx_state_info {
-  int32_t block;                /* pivots per sweep in effect                                                      */
+  int32_t block;                /* pivots per sweep of the last lpx_simplex_loop call (before any: as lpx_state_get_block) */
   int32_t chain_wgs;            /* workgroups of the last decision launch (after the residency clamp)              */
   int32_t chain_wgs_requested;  /* before the clamp                                                                */
   int32_t chain_resident_max;   /* hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs the launch could use         */
@@ -189,13 +189,14 @@ int lpx_state_read_chain_trace_fine(lpx_state* s, int64_t* ticks, int32_t cap, i
  * taken from the not-yet-updated tableau (each needs one column and one row, recovered by the pending pivots'
  * rank-1 formulas) and then applied in ONE sweep that runs every entry through the K updates in order —
  * bit-identical to K separate updates, 1/K of the HBM traffic per pivot.  0 = choose by size (default),
- * 1 = off (one update pass per pivot), 2..64 = fixed (powers of two sweep fastest; the by-size choice is 32 up to
+ * 1 = off (one update pass per pivot), 2..128 = fixed (powers of two sweep fastest; the by-size choice is 32 up to
  * ~7 GiB of tableau and 64 above: blocks of 33..64 use a two-stage sweep and 64-slot decisions, worth +3..5 % from 4 GiB;
  * shards and lpx_multi handles, and the loop with LPX_OPT_CHAIN = 0, use at most 32).  On an unsharded handle the
  * K decisions are one persistent launch and run beside the previous block's sweep, which then works out of place:
  * the handle allocates a second tableau (same size) at the first blocked loop. */
 int lpx_state_set_block(lpx_state* s, int32_t pivots_per_sweep);
-/* The value in effect (after the by-size choice): 1 = one update pass per pivot, K > 1 = K pivots per sweep. */
+/* The value in effect (after the by-size choice) for a loop with an unlimited budget: 1 = one update pass per pivot,
+ * K > 1 = K pivots per sweep.  (A call with a short budget may take shorter blocks: lpx_state_info.block.) */
 int lpx_state_get_block(const lpx_state* s);
 
 /* The loop of LPSolver.simplex                                         LPSolver.java:101-107

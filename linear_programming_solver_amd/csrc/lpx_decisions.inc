@@ -1028,6 +1028,19 @@ __device__ __forceinline__ void chain8_from(double& x, const double* c, const do
 __device__ __forceinline__ int top_bit(unsigned long long lo, unsigned long long hi) {
   return hi ? 127 - __clzll((long long)hi) : (lo ? 63 - __clzll((long long)lo) : -1);
 }
+// ... and of H ballots (bit u of w[h] = slot 64 h + u): the 128-slot rings hold 256 pending pivots, four words
+template <int H>
+__device__ __forceinline__ int top_bit_of(const unsigned long long (&w)[H]) {
+  static_assert(H == 1 || H == 2 || H == 4, "ballots of 64, 128 or 256 slots");
+  if constexpr (H == 4) {
+    const int hi = top_bit(w[2], w[3]);
+    return hi >= 0 ? 128 + hi : top_bit(w[0], w[1]);
+  } else if constexpr (H == 2) {
+    return top_bit(w[0], w[1]);
+  } else {
+    return top_bit(w[0], 0);
+  }
+}
 
 // Workgroup minimum of (ratio, row) WITH the winner's two payload values in ONE meeting: every wave reduces itself (DPP),
 // the lane that holds its wave's minimum writes the wave's record, the workgroup meets, every thread reads the NW records.
@@ -1068,11 +1081,18 @@ constexpr int kChain2Threads = 256;
 #else
 #define LPX_OWN_STORE(p_, x_) (*(p_) = (x_))
 #endif
+// The body of the decision kernels: k_block_chain2_t (ring halves of 32 / 64 slots) and k_block_decide128 (128 slots, one
+// device) below call it; the 128-slot form has a __global__ name of its own.
+// KB = 128 with NT = 256: every lane serves a pending pivot and lane 255 is the loader lane as well.  That lane's pivot is
+// slot 127 of THIS block, which is pending only for a decision s > 127: never (valid_mine stays false for it), so the two
+// roles never meet in one decision.
 template <int KB, int NT, bool MG>
-__global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
-  static_assert(KB == 32 || KB == 64, "ring half of 32 or 64 slots");
-  static_assert(NT % 64 == 0 && NT >= 256 && NT >= 2 * KB + 64, "lanes for the pending pivots and the loader lane");
+__device__ __forceinline__ void block_chain2_body(const ChainArgs& P) {
+  static_assert(KB == 32 || KB == 64 || KB == 128, "ring half of 32, 64 or 128 slots");
+  static_assert(NT % 64 == 0 && NT >= 256 && NT >= 2 * KB + (KB == 128 ? 0 : 64), "lanes for the pending pivots and the loader lane");
+  static_assert(KB <= 64 || !MG, "the shards decide at most kShardBlockMax pivots per block");
   constexpr int NC = 2 * KB / 8;   // chunks of eight pending pivots: [0, KB / 8) the previous block's, then this block's
+  constexpr int NH = (2 * KB + 63) / 64;   // 64-bit ballots over the pending pivots
   constexpr int kWin = 8;          // live chunks whose ring copies a thread holds in registers at a time
   __shared__ RatioRow sh_rr[NT / 64];
   __shared__ MinRec sh_rec[2][NT / 64];
@@ -1110,8 +1130,8 @@ __global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
   }
 #ifdef LPX_CHAIN2_LAUNCH_STAMPS   // diagnostic build (scripts/chain_launch_stamps.py): entry / first decision / last decision of the
   // launch, two sets alternating by launch, behind the per-decision stamps (8 x kBlockMax of the 16 x kBlockMax words)
-  long long* const lst = P.dbg ? P.dbg + 8 * kBlockMax + 8 * ((P.hand_base >> 6) & 1u) : nullptr;
-  if (lst && lead) { lst[0] = wall_clock64(); lst[3] = P.hand_base >> 6; }
+  long long* const lst = P.dbg ? P.dbg + 8 * kBlockMax + 8 * ((P.hand_base / (unsigned)kBlockMax) & 1u) : nullptr;
+  if (lst && lead) { lst[0] = wall_clock64(); lst[3] = P.hand_base / (unsigned)kBlockMax; }
 #endif
   if (lead) st_agent(reinterpret_cast<int32_t*>(P.bar_next), 0);
   int e = ctl->e_next;
@@ -1149,7 +1169,7 @@ __global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
   const char* const oc_n = reinterpret_cast<const char*>(P.own_col);
   const char* const op_o = reinterpret_cast<const char*>(P.own_prow_o);
   const char* const op_n = reinterpret_cast<const char*>(P.own_prow);
-  const uint32_t mp8_0 = (uint32_t)mp * 8u, ld8_0 = (uint32_t)ld * 8u;   // (launcher: 64 * max(mp, ld) * 8 < 2^32)
+  const uint32_t mp8_0 = (uint32_t)mp * 8u, ld8_0 = (uint32_t)ld * 8u;   // (launcher: kBlockMax * max(mp, ld) * 8 < 2^32)
   bool have_rec = false;   // sh_hand[1..4] hold c[e] and prow_{s-1}[e] of the record that named e (uniform)
   unsigned long long* const hand = P.hand;
   for (int i = gid; i < m; i += T) {     // this block's half of the thread's own column copies: +0 until a decision fills a slot
@@ -1197,10 +1217,10 @@ __global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
     // matches nothing): a question to LDS only, no meeting.
     int ra;
     {
-      const unsigned long long lo = __ballot(sh_e[tid & 63] == e);
-      unsigned long long hi = 0;
-      if constexpr (KB == 64) hi = __ballot(sh_e[64 + (tid & 63)] == e);
-      ra = top_bit(lo, hi);
+      unsigned long long hit[NH];
+#pragma unroll
+      for (int h = 0; h < NH; ++h) hit[h] = __ballot(sh_e[h * 64 + (tid & 63)] == e);
+      ra = top_bit_of(hit);
     }
     const int fo_a = ra < 0 ? 0 : (ra < KB ? ra + 1 : n_old);
     const int fn_a = ra >= KB ? ra - KB + 1 : 0;
@@ -1260,15 +1280,15 @@ __global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
     int reach_a[2];
     {
       const int row_w = row0 + (int)(bid * NT) + (tid & ~63);
-      unsigned long long h0[2] = {0, 0}, h1[2] = {0, 0};
+      unsigned long long h0[NH], h1[NH];
 #pragma unroll
-      for (int h = 0; h < 2 * KB / 64; ++h) {
+      for (int h = 0; h < NH; ++h) {
         const int lu = sh_l[h * 64 + (tid & 63)];
         h0[h] = __ballot((unsigned)(lu - row_w) < 64u);
         h1[h] = __ballot((unsigned)(lu - row_w - T) < 64u);
       }
-      reach_a[0] = max(ra, top_bit(h0[0], h0[1])) + 1;
-      reach_a[1] = max(ra, top_bit(h1[0], h1[1])) + 1;
+      reach_a[0] = max(ra, top_bit_of(h0)) + 1;
+      reach_a[1] = max(ra, top_bit_of(h1)) + 1;
     }
     // everything has been asked for; by the time it is here, whatever this wave stored during the previous decision has
     // long landed: the drain that makes those stores visible before this workgroup publishes anything newer is free
@@ -1320,6 +1340,16 @@ __global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
         if (L_a > kWin) {          //  a loop made the compiler copy the whole window between its prologue and its body)
           load_window_a(i, kWin);
           ladder_a(kWin);
+        }
+      }
+      if constexpr (NC > 2 * kWin) {   // (a 128-slot launch: up to four windows, each a round trip of its own, unrolled as above;
+        if (L_a > 2 * kWin) {          //  the boundary value a_mid is caught inside whichever window holds chunk Lo_a)
+          load_window_a(i, 2 * kWin);
+          ladder_a(2 * kWin);
+        }
+        if (L_a > 3 * kWin) {
+          load_window_a(i, 3 * kWin);
+          ladder_a(3 * kWin);
         }
       }
       if (Lo_a >= L_a) a_mid = a;   // no pivot of this block behind the boundary
@@ -1469,10 +1499,10 @@ __global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
     // restarts from the thread's copy of that row (every wave asks for itself, as in phase A)
     int rb;
     {
-      const unsigned long long lo = __ballot(sh_l[tid & 63] == l);
-      unsigned long long hi = 0;
-      if constexpr (KB == 64) hi = __ballot(sh_l[64 + (tid & 63)] == l);
-      rb = top_bit(lo, hi);
+      unsigned long long hit[NH];
+#pragma unroll
+      for (int h = 0; h < NH; ++h) hit[h] = __ballot(sh_l[h * 64 + (tid & 63)] == l);
+      rb = top_bit_of(hit);
     }
     // On shards only the device that holds row l computes it; the others receive the normalised row (below).
     const bool owner = !MG || (l >= row0 && l < row0 + m);
@@ -1542,15 +1572,15 @@ __global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
     int reach_b[2];
     {
       const int col_w = __builtin_amdgcn_readfirstlane(jfirst);   // (a wave's lanes own consecutive slots)
-      unsigned long long h0[2] = {0, 0}, h1[2] = {0, 0};
+      unsigned long long h0[NH], h1[NH];
 #pragma unroll
-      for (int h = 0; h < 2 * KB / 64; ++h) {
+      for (int h = 0; h < NH; ++h) {
         const int eu = sh_e[h * 64 + (tid & 63)];
         h0[h] = __ballot((unsigned)(eu - col_w) < 64u);
         h1[h] = __ballot((unsigned)(eu - col_w - jstep) < 64u);
       }
-      reach_b[0] = max(rb, top_bit(h0[0], h0[1])) + 1;
-      reach_b[1] = max(rb, top_bit(h1[0], h1[1])) + 1;
+      reach_b[0] = max(rb, top_bit_of(h0)) + 1;
+      reach_b[1] = max(rb, top_bit_of(h1)) + 1;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (as in phase A: also the free drain of this wave's earlier stores)
     if (P.dbg && lead) P.dbg[s * LPX_C2_STRIDE + 4] = wall_clock64();   // this wave's loads of phase B are here
@@ -1597,6 +1627,16 @@ __global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
           if (L_b > kWin) {
             load_window_b(j, kWin);
             ladder_b(kWin);
+          }
+        }
+        if constexpr (NC > 2 * kWin) {
+          if (L_b > 2 * kWin) {
+            load_window_b(j, 2 * kWin);
+            ladder_b(2 * kWin);
+          }
+          if (L_b > 3 * kWin) {
+            load_window_b(j, 3 * kWin);
+            ladder_b(3 * kWin);
           }
         }
         if (Lo_b >= L_b) x_mid = x;
@@ -1749,6 +1789,16 @@ __global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
     e = e_next;
     lds_barrier();   // sh_e[KB + s] .. and sh_hand are read by the next decision; sh_mask / sh_win are rewritten
   }
+}
+template <int KB, int NT, bool MG>
+__global__ __launch_bounds__(NT) void k_block_chain2_t(const ChainArgs P) {
+  static_assert(KB == 32 || KB == 64, "ring half of 32 or 64 slots");
+  block_chain2_body<KB, NT, MG>(P);
+}
+// Blocks of 65..128 pivots (one device): 256 pending pivots, 32 chunks, up to four windows per ladder.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_block_decide128(const ChainArgs P) {
+  block_chain2_body<128, NT, false>(P);
 }
 #undef LPX_C2_STAMP
 #undef LPX_C2_STRIDE

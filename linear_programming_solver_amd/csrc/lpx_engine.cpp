@@ -597,8 +597,9 @@ static int build_block_ring(lpx_state* s) {
   HIP_TRY(hipMemsetAsync(s->R.sweep_fail, 0, 128, s->stream));
   HIP_TRY(hipMalloc((void**)&s->R.clk, 256));
   HIP_TRY(hipMemsetAsync(s->R.clk, 0, 256, s->stream));
-  HIP_TRY(hipMalloc((void**)&s->R.col_packed, 2 * (size_t)(mp / 4 + 1) * 2048));
-  HIP_TRY(hipMemsetAsync(s->R.col_packed, 0, 2 * (size_t)(mp / 4 + 1) * 2048, s->stream));
+  // (1 KiB per row and ring half: k_sweep128_mfma's 16 KiB per 16-row tile; the 64-pivot kernels use half of it)
+  HIP_TRY(hipMalloc((void**)&s->R.col_packed, 2 * (size_t)(mp / 4 + 1) * 4 * lpxk::kColPackedRowBytes));
+  HIP_TRY(hipMemsetAsync(s->R.col_packed, 0, 2 * (size_t)(mp / 4 + 1) * 4 * lpxk::kColPackedRowBytes, s->stream));
   HIP_TRY(hipMalloc((void**)&s->d_cand, (size_t)(LPX_CAND_HEADER + s->B.ld) * sizeof(double)));
   HIP_TRY(hipMemsetAsync(s->R.prow, 0, K * (size_t)s->B.ld * sizeof(double), s->stream));
   HIP_TRY(hipMemsetAsync(s->R.col, 0, K * (size_t)mp * sizeof(double), s->stream));
@@ -625,11 +626,14 @@ int ensure_spare_tableau(lpx_state* s) {
   return 0;
 }
 
+constexpr double kBlock128MinSweepUs = 1400.0;   // 16 m ld / 6e6: 4 GiB tableaux (cfg4: 1431)
+constexpr int64_t kBlock128MinBudget = 256;      // two full blocks
 // Pivots per sweep.  Measured on MI355X: one decision (peek + pack + commit, three latency-bound launches) costs
 // ~18 us + ~0.4 us per pending pivot whatever the size; a sweep moves the tableau once at ~5.6 TB/s up to K = 16
 // and at ~4.7 TB/s at K = 32 (there the 2K fp64 operations per entry co-limit it); the one-pass form costs one
 // pass at ~6.3 TB/s + ~9 us per pivot.  Per pivot: blocked(K) ~ 18 + 0.4 K/2 + sweep(K)/K.
-int choose_block(const lpx_state* s) {
+// max_pivots: the budget of the loop call that asks (< 0: unlimited, also what lpx_state_get_block asks for).
+int choose_block(const lpx_state* s, int64_t max_pivots) {
   int K = (int)s->opt[LPX_OPT_BLOCK];
   if (K == 0) {
     const double sweep_us = 16.0 * (double)s->m * (double)s->B.ld / 6.0e6;
@@ -657,7 +661,20 @@ int choose_block(const lpx_state* s) {
     // 0.875 GiB (8192 x 14336) 73.3k / 75.7k, 1 GiB (cfg3) 67.7k / 73.7k; round 4 above: 1.25 GiB 48.0k / 53.0k,
     // cfg4 18.2k / 27.5k (profiles/r04_block_by_size_fused.txt).  From ~0.85 GiB.
     if (s->B.fused && sweep_us >= 300.0 && s->m % 16 == 0 && s->B.ld >= 512 && s->m_global == s->m) K = 64;
+    // 128 (fused arithmetic, whole strips of 16-row tiles, one device): k_sweep128_mfma shares one pass over memory among
+    // twice the pivots and runs at the matrix pipe's floor (EXPERIMENTS 000.55: 2.80 ms per 128 pivots against 2 x 1.9 ms on
+    // 192 CUs at cfg4).  It pays where the sweep sets the pace of the loop and the 128 decisions of a block hide behind a
+    // sweep: from 4 GiB (cfg4) up; cfg3 (1 GiB) is bound by its decisions and keeps 64.  A block of 128 decisions in front of
+    // the first sweep is not hidden (~1.9 ms against ~0.95 ms for 64), so a call whose budget fits one or two blocks keeps
+    // 64 (break-even estimated at ~110 pivots): 128 only for an unlimited budget or one of at least kBlock128MinBudget.
+    // (EXPERIMENTS "blocks of 128 pivots, end to end".)
+    if (K == 64 && s->B.fused && sweep_us >= kBlock128MinSweepUs && s->B.ld % 512 == 0 && s->m_global == s->m && !s->multi_shard &&
+        s->opt[LPX_OPT_CHAIN] != 0 && s->opt[LPX_OPT_OVERLAP] != 0 && (max_pivots < 0 || max_pivots >= kBlock128MinBudget))
+      K = 128;
   }
+#ifdef LPX_WITH_VARIANTS   // (chain_form = 0 on one device, the variants library only: round 3's kernel holds 64 pending pivots)
+  if (s->B.chain_form != 1) K = std::min(K, 64);
+#endif
   // three launches per decision (option chain = 0, the form the shards use): its kernels hold at most 32 pending pivots
   if (!s->opt[LPX_OPT_CHAIN] || s->m_global != s->m) K = std::min(K, (int)lpxk::kShardBlockMax);
   return std::max(1, std::min(K, (int)lpxk::kBlockMax));
@@ -732,7 +749,7 @@ lpxk::BlockRing ring_half(const lpx_state* s, int h) {
   R.col0 += o * R.mp;
   if (R.fix_col) R.fix_col += o * R.mp;
   if (R.fix_row) R.fix_row += o * s->B.ld;
-  if (R.col_packed) R.col_packed += (int64_t)h * (R.mp / 4 + 1) * (2048 / sizeof(double));
+  if (R.col_packed) R.col_packed += (int64_t)h * (R.mp / 4 + 1) * (4 * lpxk::kColPackedRowBytes / sizeof(double));
   if (R.tickets) R.tickets += (int64_t)h * lpxk::sweep_ticket_slots(s->B.ld) * 32;
   R.up += o;
   return R;
@@ -1047,7 +1064,8 @@ static int blocked_loop(lpx_state* s, int K, int64_t max_pivots, const lpxk::Loo
   return rc;
 }
 
-extern "C" int lpx_state_get_block(const lpx_state* s) { return s ? choose_block(s) : -1; }
+// (what an unbounded loop of this handle would take)
+extern "C" int lpx_state_get_block(const lpx_state* s) { return s ? choose_block(s, -1) : -1; }
 
 // ---- blocked pivoting on row-block shards: the host exchanges the candidate of every decision ---------------
 extern "C" int lpx_shard_block_peek(lpx_state* s, double* d_candidate, int32_t slot) {
@@ -1081,8 +1099,9 @@ extern "C" int lpx_shard_block_sweep(lpx_state* s, int32_t nslots) {
 
 extern "C" int lpx_state_set_block(lpx_state* s, int32_t pivots_per_sweep) {
   if (!s || pivots_per_sweep < 0 || pivots_per_sweep > lpxk::kBlockMax)
-    return fail(LPX_BAD_ARGUMENT, "lpx_state_set_block: 0 (auto), 1 (off) .. 64");
+    return fail(LPX_BAD_ARGUMENT, "lpx_state_set_block: 0 (auto), 1 (off) .. 128");
   s->opt[LPX_OPT_BLOCK] = pivots_per_sweep;
+  s->loop_block = 0;
   return 0;
 }
 
@@ -1095,6 +1114,7 @@ extern "C" int lpx_state_set_option(lpx_state* s, int32_t key, int64_t value) {
   if ((key == LPX_OPT_CHAIN_CUS || key == LPX_OPT_SWEEP_CUS) && s->ov_chain && value != s->opt[key])
     return fail(LPX_BAD_ARGUMENT, "lpx_state_set_option: the CU-masked stream pair of this handle exists already (set CHAIN_CUS / SWEEP_CUS before the first blocked loop)");
   s->opt[key] = value;
+  s->loop_block = 0;   // lpx_state_info.block: the answer for the new options until a loop has run with them
   if (key == LPX_OPT_CHAIN_FORM) s->B.chain_form = (int)value;
   if (key == LPX_OPT_FUSED) resolve_arithmetic(s);   // which of the two compilations of the kernels the launches take
   if (key == LPX_OPT_UPDATE_U || key == LPX_OPT_UPDATE_ROWS || key == LPX_OPT_NT) apply_layout_options(s);
@@ -1112,7 +1132,7 @@ extern "C" int lpx_state_get_option(const lpx_state* s, int32_t key, int64_t* va
 extern "C" int lpx_state_get_info(lpx_state* s, lpx_state_info* out) {
   if (!s || !out) return fail(LPX_BAD_ARGUMENT, "lpx_state_get_info: NULL argument");
   HIP_TRY(hipSetDevice(s->device));
-  s->info.block = choose_block(s);
+  s->info.block = s->loop_block > 0 ? s->loop_block : choose_block(s, -1);   // what the last loop call did / would do
   s->info.arith_fused = s->B.fused ? 1 : 0;
   s->info.chain_xcd_mask = 0;
   s->info.sweep_xcd_mask = 0;
@@ -1211,7 +1231,8 @@ extern "C" int lpx_simplex_loop(lpx_state* s, int64_t max_pivots, int64_t* pivot
                                 int32_t* track_slot) {
   if (int rc = require_single(s, "lpx_simplex_loop")) return rc;
   HIP_TRY(hipSetDevice(s->device));
-  const int K = choose_block(s);
+  const int K = choose_block(s, max_pivots);
+  s->loop_block = K;
   if (K >= 2) {
     // one host round trip per call: the first launch of the loop starts the loop state over on the device (no
     // read-modify-write of the host mirror in front), the last copy brings it back in front of the loop's own final wait

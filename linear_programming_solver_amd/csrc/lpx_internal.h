@@ -46,6 +46,7 @@ struct lpx_state {
   int pricing = 0;                  // 0 = reference rule (first positive), 1 = Dantzig (opt-in extension)
   int64_t opt[LPX_OPT_COUNT] = {};  // lpx_option values (include/lpx.h); initial values: env_defaults()
   lpx_state_info info{};            // what the last loop actually did (lpx_state_get_info)
+  int loop_block = 0;               // pivots per sweep of the last lpx_simplex_loop call (0: none since the options changed)
   int chain_nb_last = 0;            // decisions of the last k_block_chain launch (chain trace)
   bool peer_written = false;        // a shard of an lpx_multi on several devices: buffers that peers store into
   bool multi_shard = false;     // a shard of an lpx_multi (also with a single shard / all shards on one GPU)
@@ -106,7 +107,7 @@ int ensure_overlap_streams(lpx_state* s);   // ov_chain / ov_sweep (CU-masked wh
 // hipMalloc, or fine-grained device memory when peers store into the buffer while a kernel of this device reads it
 hipError_t peer_visible_malloc(const lpx_state* s, void** ptr, size_t bytes);
 int32_t state_n(const lpx_state* s);
-int choose_block(const lpx_state* s);
+int choose_block(const lpx_state* s, int64_t max_pivots = -1);
 int block_len(int K, int64_t max_pivots, int64_t decided);
 int clamp_chain_wgs(lpx_state* s, int want, int cus);
 int device_cus(const lpx_state* s);

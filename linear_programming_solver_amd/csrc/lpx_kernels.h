@@ -62,7 +62,7 @@ struct Buffers {
 };
 
 // blocked pivoting: ring of pending pivots (see lpx_kernels.hip "blocked pivoting")
-constexpr int kBlockMax = 64;        // pivots per block / slots per ring half (single-device loop)
+constexpr int kBlockMax = 128;       // pivots per block / slots per ring half (single-device loop)
 constexpr int kShardBlockMax = 32;   // the step-wise shard interface and lpx_multi decide at most this many per block
 constexpr int kChainMaxWgs = 256;   // <= one workgroup per CU: the whole grid is resident
 constexpr int kMaxDevices = 8;      // row-block shards of one lpx_multi (the GPUs of one node)
@@ -86,8 +86,8 @@ struct BlockRing {  // every ring has 2 * kBlockMax slots: two halves, one per b
   unsigned* census;        // [w] = XCC id + 1 of chain workgroup w; [kChainMaxWgs] = OR of (1 << XCC id) of sampled sweep workgroups
   double* fix_col;         // overlapped loop: images of the fix-up's entering columns [chain][mp] (NULL: the fix-up follows the sweep and writes the tableau itself)
   double* fix_row;         // ... and of its pivot rows [chain][ld]; both 2 x kBlockMax chains like the rings
-  double* col_packed;      // k_sweep32_pull: the block's multipliers as [batch of 4 rows][pivot][row]: (mp / 4) x 1 KiB (2 KiB for blocks of 64)
-  unsigned* tickets;       // k_sweep32_pull: one batch counter per 128-column sub-strip, 128 bytes apart (ld / 128 of them); like col_packed once per ring half
+  double* col_packed;      // k_sweep32_pull: the block's multipliers as [batch of 4 rows][pivot][row]: (mp / 4) x 1 KiB (2 KiB for blocks of 64, 4 KiB for k_sweep128_mfma: 16 KiB per 16-row tile)
+  unsigned* tickets;       // k_sweep32_pull: one batch counter per 128-column sub-strip, 128 bytes apart (sweep_ticket_slots(ld) of them: k_sweep128_mfma takes one chunk counter and one per (64-column sub-strip, row range)); like col_packed once per ring half
   unsigned* sweep_fail;    // the word a pull kernel sets when a bounded wait ran out (k_sweep64_pull: variants library only)
   long long* clk;          // clock probe of the last pulled sweep, per XCD x: clk[4 x + 0..1] = {s_memtime, 100 MHz} in front of it, [4 x + 2..3] behind it
   const double* zeros;     // 256 bytes of +0.0: what k_sweep32_dma's multiplier DMA reads for the identity steps of a partly filled block
@@ -112,11 +112,13 @@ struct MgPeers {
   unsigned spin_max;                       // bound of the waits between devices in polls (0: the default, 2^22 = seconds)
 };
 // which kernel swept the bulk of the tableau (lpx_state_info.sweep_kernel)
-enum SweepKernel { kSweepNone = 0, kSweepTiles = 1, kSweepMulti = 2, kSweepSteady = 3, kSweepPipe64 = 4, kSweepDma = 5, kSweepPull = 6, kSweepPull64 = 7, kSweepOne64 = 8, kSweepMfma64 = 9, kSweepMfma642 = 10 };
+enum SweepKernel { kSweepNone = 0, kSweepTiles = 1, kSweepMulti = 2, kSweepSteady = 3, kSweepPipe64 = 4, kSweepDma = 5, kSweepPull = 6, kSweepPull64 = 7, kSweepOne64 = 8, kSweepMfma64 = 9, kSweepMfma642 = 10, kSweepMfma128 = 11 };
 // The fix-up of a block beside its sweep (launch_block_sweep): where its chains run and the two events that tie them in.
 // ready: the block's decisions are through (the side stream waits for it); packed: the sweep's pack kernel is through (may be
 // NULL: it then runs on the sweep's stream); done: the fix-up's chains are through (the copy kernel waits for it).
 struct FixSide { hipStream_t stream; hipEvent_t ready, done, packed; };
+constexpr int kColPackedRowBytes = 1024;   // BlockRing::col_packed per ring half: (mp / 4 + 1) batches of 4 x this many bytes
+constexpr int kSweep128Ranges = 3;        // k_sweep128_mfma: row ranges per 64-column sub-strip (micro-benchmark at cfg4: 3 2.80 ms, 12 2.87, 32 2.97)
 struct RestoreEntry { int32_t is_basic; int32_t index; double k; };  // index = row r (basic) or post-drop slot
 
 // ---- batched solve (lpx_batch.inc / lpx_batch.cpp): many small LPs, one workgroup per LP, the whole state in LDS ----

@@ -968,6 +968,7 @@ int launch_block_chain(const Buffers& B, const BlockRing& R, int n, int m, int n
   }
   const int64_t K = kBlockMax;
   const bool wide = nb > 32 || n_old > 32;   // a block of more than 32 pivots on either side: the 64-slot form
+  const bool wide128 = nb > 64 || n_old > 64;   // ... of more than 64: the 128-slot kernel (one device)
   ChainArgs P{};
   P.A = B.A; P.b = B.b; P.ld = B.ld; P.mp = R.mp; P.n = n; P.m = m;
   P.c = B.c; P.perm = B.perm; P.ctl = B.ctl;
@@ -983,7 +984,7 @@ int launch_block_chain(const Buffers& B, const BlockRing& R, int n, int m, int n
   P.partA = reinterpret_cast<ChainPart*>(R.chain_part_a); P.partB = reinterpret_cast<RatioRow*>(R.chain_part_b);
   P.bar = R.chain_bar + 32 * (seq & 1); P.bar_next = R.chain_bar + 32 * ((seq + 1) & 1);
   P.hand = reinterpret_cast<unsigned long long*>(R.chain_bar + 64);   // its own 128-byte line
-  P.hand_base = (unsigned)(seq + 1) * 64u;  // > any sequence of earlier launches (<= kBlockMax decisions each)
+  P.hand_base = (unsigned)(seq + 1) * (unsigned)kBlockMax;  // > any sequence of earlier launches (<= kBlockMax decisions each)
   P.dantzig = dantzig; P.fences = fences; P.host_snap = host_snap; P.dbg = trace ? R.chain_dbg : nullptr;
   P.spin_max = (mg && mg->spin_max) ? mg->spin_max : (1u << 22);
 #ifdef LPX_DIAG_BUILD   // timing experiments only (results are wrong): never in the release library
@@ -1010,11 +1011,13 @@ int launch_block_chain(const Buffers& B, const BlockRing& R, int n, int m, int n
     P.m_global = m; P.n_dev = 1;
 #ifdef LPX_CHAIN2_ONE_XCD
     G = std::min(G, 32);
-    if (wide) hipLaunchKernelGGL((k_block_chain2_t<64, kChain2Threads, false>), dim3(8 * G), dim3(kChain2Threads), 0, s, P);
+    if (wide128) hipLaunchKernelGGL((k_block_decide128<kChain2Threads>), dim3(8 * G), dim3(kChain2Threads), 0, s, P);
+    else if (wide) hipLaunchKernelGGL((k_block_chain2_t<64, kChain2Threads, false>), dim3(8 * G), dim3(kChain2Threads), 0, s, P);
     else hipLaunchKernelGGL((k_block_chain2_t<32, kChain2Threads, false>), dim3(8 * G), dim3(kChain2Threads), 0, s, P);
     if (stop) (void)hipEventRecord(stop, s);
 #else
-    if (wide) LPX_LAUNCH_STOP((k_block_chain2_t<64, kChain2Threads, false>), dim3(G), dim3(kChain2Threads), s, stop, P);
+    if (wide128) LPX_LAUNCH_STOP((k_block_decide128<kChain2Threads>), dim3(G), dim3(kChain2Threads), s, stop, P);
+    else if (wide) LPX_LAUNCH_STOP((k_block_chain2_t<64, kChain2Threads, false>), dim3(G), dim3(kChain2Threads), s, stop, P);
     else LPX_LAUNCH_STOP((k_block_chain2_t<32, kChain2Threads, false>), dim3(G), dim3(kChain2Threads), s, stop, P);
 #endif
   } else {
@@ -1037,7 +1040,8 @@ int launch_block_chain(const Buffers& B, const BlockRing& R, int n, int m, int n
 // no rows, no decisions) and touch nothing but the ring's own words.
 // The ticket buffer: one 128-byte slot per 128-column sub-strip (at least the four the preparing launches pull from),
 // then spare slots.  (The word a pull kernel sets when a bounded wait ran out is BlockRing::sweep_fail.)
-int64_t sweep_ticket_slots(int64_t ld) { return std::max<int64_t>(ld / 64, 4) + 4; }   // (k_sweep64_one: a counter per 64 columns)
+// (k_sweep64_one: a counter per 64 columns; k_sweep128_mfma: the chunk counter + one per (64 columns, row range))
+int64_t sweep_ticket_slots(int64_t ld) { return kSweep128Ranges * std::max<int64_t>(ld / 64, 4) + 4; }
 unsigned* sweep_fail_word(const BlockRing& R, int64_t ld) {
 #ifdef LPX_WITH_VARIANTS   // (the only kernel that sets it, k_sweep64_pull, is in the variants library only)
   (void)ld;
@@ -1105,6 +1109,12 @@ void preload_block_kernels(const Buffers& B, const BlockRing& R, hipStream_t s) 
     hipLaunchKernelGGL((k_sweep64_mfma2<NT_, OOP_>), dim3(1), dim3(256), 0, s, A, A, ld, 0, R.prow, R.up, 0, 1, R.col_packed, R.tickets, 33, (long long*)nullptr);
     LPX_EACH_NT_OOP(LPX_PRE_MFMA642)
 #undef LPX_PRE_MFMA642
+    // (no tile to pack, no chunk to pull: each returns behind its first look)
+    hipLaunchKernelGGL(k_pack_multipliers_mfma128, dim3(1), dim3(256), 0, s, R.col, R.mp, R.up, 0, 0, R.col_packed, R.tickets, 0, (long long*)nullptr);
+#define LPX_PRE_MFMA128(NT_, OOP_) \
+    hipLaunchKernelGGL((k_sweep128_mfma<NT_, OOP_>), dim3(1), dim3(256), 0, s, A, A, ld, 0, R.prow, R.up, 0, 0, R.col_packed, R.tickets, 1);
+    LPX_EACH_NT_OOP(LPX_PRE_MFMA128)
+#undef LPX_PRE_MFMA128
 #endif
   }
 #undef LPX_PRE_PULL
@@ -1135,20 +1145,22 @@ void preload_block_kernels(const Buffers& B, const BlockRing& R, hipStream_t s) 
   hipLaunchKernelGGL((k_block_chain2_t<32, kChain2Threads, false>), dim3(1), dim3(kChain2Threads), 0, s, P);
   hipLaunchKernelGGL((k_block_chain2_t<64, kChain2Threads, false>), dim3(1), dim3(kChain2Threads), 0, s, P);
   hipLaunchKernelGGL((k_block_chain2_t<32, kChain2Threads, true>), dim3(1), dim3(kChain2Threads), 0, s, P);
+  hipLaunchKernelGGL((k_block_decide128<kChain2Threads>), dim3(1), dim3(kChain2Threads), 0, s, P);
   (void)hipGetLastError();
 }
 
 int chain_blocks_per_cu() {
   int nb = 0;
   int nw = 0;
-  int n2 = 0;
+  int n2 = 0, n3 = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_block_chain_t<true, 32>), 256, 0) != hipSuccess ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&nw, (k_block_chain2_t<32, kChain2Threads, false>), kChain2Threads, 0) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, (k_block_chain2_t<64, kChain2Threads, true>), kChain2Threads, 0) != hipSuccess) {
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, (k_block_chain2_t<64, kChain2Threads, true>), kChain2Threads, 0) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&n3, (k_block_decide128<kChain2Threads>), kChain2Threads, 0) != hipSuccess) {
     (void)hipGetLastError();
-    nb = nw = n2 = 1;
+    nb = nw = n2 = n3 = 1;
   }
-  return std::max(1, std::min(std::min(nb, nw), n2));
+  return std::max(1, std::min(std::min(nb, nw), std::min(n2, n3)));
 }
 
 template <int K>
@@ -1268,6 +1280,28 @@ static void launch_sweep64_mfma(const Buffers& B, const BlockRing& R, int m_loca
 }
 #endif
 
+#if LPX_FUSED
+// blocks of 65..128 on the matrix cores (fused arithmetic, whole strips): k_sweep128_mfma, two workgroups per CU, each bound
+// to one 64-column sub-strip at a time; chunks (sub-strip, row range) pulled from the first ticket counter, the chunk's
+// 16-row tiles from the chunk's own
+static void launch_sweep128_mfma(const Buffers& B, const BlockRing& R, int m_local, int kmax, bool nt, const double* A_src,
+                                 hipStream_t s, int cus, const FixSide* side, hipEvent_t t0, hipEvent_t t1) {
+  const int nsub = (int)(B.ld / 64);
+  const int ntiles = m_local / 16;
+  const int nranges = std::max(1, std::min(kSweep128Ranges, ntiles));
+  LPX_LAUNCH_STOP(k_pack_multipliers_mfma128, dim3(ntiles), dim3(256), pack_stream(side, s), pack_stop(side), R.col, R.mp, R.up, kmax,
+                  ntiles, R.col_packed, R.tickets, 1 + nsub * nranges, R.clk);
+  pack_done(side, s);
+  const dim3 grid(std::max(1, std::min(2 * cus, nsub * nranges))), block(256);
+#define LPX_LAUNCH_MFMA128(NT_, OOP_)                                                                                    \
+  LPX_LAUNCH_TIMED((k_sweep128_mfma<NT_, OOP_>), grid, block, s, t0, t1, B.A, A_src, B.ld, m_local, R.prow, R.up, kmax, nsub, \
+                   R.col_packed, R.tickets, nranges)
+  if (A_src) { if (nt) LPX_LAUNCH_MFMA128(true, true); else LPX_LAUNCH_MFMA128(false, true); }
+  else { if (nt) LPX_LAUNCH_MFMA128(true, false); else LPX_LAUNCH_MFMA128(false, false); }
+#undef LPX_LAUNCH_MFMA128
+}
+#endif
+
 static int choose_sweep_rows(int m_local, int64_t ld, int K, int cus) {
   const int64_t nstrips = (ld + 511) / 512;
   const int64_t slots = std::max(1, 2 * cus);
@@ -1299,6 +1333,7 @@ const char* sweep_kernel_name(int code) {
     case kSweepOne64: return "k_sweep64_one";
     case kSweepMfma64: return "k_sweep64_mfma";
     case kSweepMfma642: return "k_sweep64_mfma2";
+    case kSweepMfma128: return "k_sweep128_mfma";
     default: return "";
   }
 }
@@ -1349,6 +1384,34 @@ int launch_block_sweep(const Buffers& B, const BlockRing& R, int n, int m_local,
     else launch_sweep_tiles<16>(B, R, m_local, K, rows_per_tile, nt, A_src, s);
     rows_per_wg = rows_per_tile;
     used = kSweepTiles;
+  } else if (K > 64) {
+    // blocks of 65..128 pivots.  Fused arithmetic over whole strips of 16-row tiles: ONE pass of k_sweep128_mfma (its pack kernel
+    // on the side stream, like k_sweep64_mfma2's) — also where the block ended early: the identity steps of a partly filled
+    // block are exact, and such a block is the last of its loop.  Everything else (the default arithmetic, a partial last
+    // strip, m not a multiple of 16) takes four passes of the generic kernel over slots 0.., 32.., 64.., 96..: the first out
+    // of place when asked, the others in place on its result.  An entry's update reads ring values only, so the split
+    // changes no bit; that path is correct but slow, and no policy chooses it by size.
+    bool mfma128 = false;
+#if LPX_FUSED
+    mfma128 = form != 3 && m_local % 16 == 0 && m_local >= 16 && B.ld % 512 == 0 && 16 * B.ld * 8 + 1024 < ((int64_t)1 << 32) &&
+              R.tickets && R.col_packed;
+#endif
+    if (mfma128) {
+#if LPX_FUSED
+      timed_own = before_sweep && after_sweep;
+      if (!timed_own) bracket();
+      launch_sweep128_mfma(B, R, m_local, K, nt, A_src, s, cus, side, timed_own ? before_sweep : nullptr, timed_own ? after_sweep : nullptr);
+#endif
+      rows_per_wg = 16;
+      used = kSweepMfma128;
+    } else {
+      bracket();
+      int rows = choose_sweep_rows(m_local, B.ld, 32, cus);
+      while (rows > kSweepChunk && (int64_t)rows * B.ld * 8 >= (int64_t)1 << 32) rows -= kSweepChunk;
+      for (int slot0 = 0; slot0 < K; slot0 += 32) launch_sweep_k<32>(B, R, m_local, K, rows, nt, slot0 == 0 ? A_src : nullptr, s, 0, slot0);
+      rows_per_wg = rows;
+      used = kSweepMulti;
+    }
   } else if (K > 32) {
     // blocks of up to 64 pivots.  A block of 33..64 valid pivots over the full strips goes through a 64-step kernel in one
     // pass (k_sweep64_one: one wave per 64-column sub-strip; in the fused arithmetic with 16-row tiles k_sweep64_mfma2, the
@@ -1482,7 +1545,7 @@ int launch_block_sweep(const Buffers& B, const BlockRing& R, int n, int m_local,
     (void)hipStreamWaitEvent(s, side->done, 0);
   }
   // `stop` (the caller's "this block's sweep is through"): the stop event of the last kernel — unless the probe's memset follows
-  const bool memset_behind = !probed && R.clk;
+  const bool memset_behind = !probed && R.clk && used != kSweepMfma128;   // (its pack kernel cleared the probe's words)
   hipEvent_t last_stop = memset_behind ? nullptr : stop;
   if (side_fix) {
     LPX_LAUNCH_STOP(k_block_fixup_scatter, dim3(gx, (K + kFixChunk - 1) / kFixChunk, 2), dim3(256), s, last_stop, B.A, B.ld, m_local, row0,

@@ -31,6 +31,19 @@ __device__ __forceinline__ int ring_count(const LpxCtl* __restrict__ ring, int k
   __syncthreads();
   return *sh_np;
 }
+// ... of a ring half of up to 128 slots (blocks of 65..128 pivots): two looks
+__device__ __forceinline__ int ring_count128(const LpxCtl* __restrict__ ring, int kmax, int* sh_np) {
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    const unsigned long long m0 = __ballot(lane < kmax && ring[lane].do_update != 0);
+    const unsigned long long m1 = __ballot(lane + 64 < kmax && ring[lane + 64].do_update != 0);
+    const int n0 = (~m0 == 0ull) ? 64 : (__ffsll((long long)~m0) - 1);
+    const int n1 = (~m1 == 0ull) ? 64 : (__ffsll((long long)~m1) - 1);
+    if (lane == 0) *sh_np = n0 < 64 ? n0 : 64 + n1;
+  }
+  __syncthreads();
+  return *sh_np;
+}
 
 // The K-fold update of one batch of RB rows x one double2 held in registers; the multipliers come from LDS
 // (one 16-byte broadcast read = two rows).  PIPE: the steady-state form — straight-line code with the LDS reads of
@@ -249,7 +262,7 @@ __global__ __launch_bounds__(256, LPX_SWEEP_LB(K)) void k_update_multi(double* _
   __shared__ int sh_np;
   constexpr int CH = kSweepChunk;
   if (complement) {
-    const int np0 = ring_count(ring, kBlockMax, kmax, &sh_np);
+    const int np0 = ring_count(ring, 64, kmax, &sh_np);   // (the kernels in front take blocks of at most 64)
     if (np0 >= complement - 1 && (blockIdx.x % nstrips + 1) * 512 <= (int)ld) return;
     __syncthreads();
   }
@@ -282,8 +295,11 @@ __global__ __launch_bounds__(256, LPX_SWEEP_LB(K)) void k_update_multi(double* _
 
   // Prologue, once per workgroup: the ring's flags, the first chunk's multipliers, the thread's slices of the K pivot
   // rows and the first batch of rows are requested together — ONE memory round trip, not four.
-  bool ok = false;
-  if (threadIdx.x < 64) ok = (int)threadIdx.x < kmax && ring[threadIdx.x].do_update != 0;   // kmax <= 64 slots
+  bool ok = false, ok_hi = false;   // kmax <= 128 slots: lane u looks at slot u and, in a block of more than 64, at slot 64 + u
+  if (threadIdx.x < 64) {
+    ok = (int)threadIdx.x < kmax && ring[threadIdx.x].do_update != 0;
+    if (kmax > 64) ok_hi = (int)threadIdx.x + 64 < kmax && ring[threadIdx.x + 64].do_update != 0;
+  }
   for (int idx = threadIdx.x; idx < K * CH; idx += 256) {
     const int sidx = idx / CH, r = idx % CH;
     sh_col[sidx][r] = (r < nrows) ? col_ring[(int64_t)sidx * mp + r_begin + r] : 0.0;  // slots >= np: never used
@@ -309,8 +325,10 @@ __global__ __launch_bounds__(256, LPX_SWEEP_LB(K)) void k_update_multi(double* _
   }
   if (threadIdx.x < 64) {
     const unsigned long long mask = __ballot(ok);
+    const unsigned long long mask_hi = kmax > 64 ? __ballot(ok_hi) : 0ull;   // (uniform)
     if (threadIdx.x == 0) {
-      const int np_block = (~mask == 0ull) ? 64 : (__ffsll((long long)~mask) - 1);   // leading valid slots of the block
+      int np_block = (~mask == 0ull) ? 64 : (__ffsll((long long)~mask) - 1);   // leading valid slots of the block
+      if (np_block == 64) np_block += (~mask_hi == 0ull) ? 64 : (__ffsll((long long)~mask_hi) - 1);
       sh_np = max(0, min(K, np_block - slot0));
     }
   }
@@ -1117,6 +1135,178 @@ __global__ __launch_bounds__(256, 2) void k_sweep64_mfma2(double* A, const doubl
 }
 
 #undef LPX_MFMA_FENCE
+// ---- k_sweep128_mfma: a block of up to 128 pivots per pass (EXPERIMENTS 000.55; scripts/micro/sweep_mfma128.hip
+// compares it bit for bit with two passes of k_sweep64_mfma2).
+// Twice the arithmetic per memory pass puts the kernel at the matrix pipe's floor (the projection: 2.63 ms per 128 pivots on 192
+// CUs).  What changes against k_sweep64_mfma2:
+//  * the B operands of 128 pivots take 64 KiB for ONE 64-column sub-strip: a workgroup (four waves, two workgroups per CU as
+//    before) is bound to a sub-strip, not to a 128-column group;
+//  * 256 sub-strips at n = 16384 do not divide 2 x 192 resident workgroups, so the binding is not static: a workgroup pulls
+//    CHUNKS (sub-strip, row range) from tickets[0] — chunks of one row range are adjacent sub-strips, so the workgroups running
+//    side by side still cover whole rows —, loads the sub-strip's B operands if it changed, and its waves pull the chunk's
+//    16-row tiles from the chunk's own counter (tickets[32 * (1 + chunk)]);
+//  * two tile buffers instead of three (a tile's A operands are 32 doubles per lane: c 2 x 32 + a 2 x 64 VGPRs): the arithmetic of a
+//    tile is twice as long, one tile ahead is as much time as two were;
+//  * a ticket is pulled a step before it is taken, as there: the wait in front of the take covers the 32 loads, 16 stores and
+//    the next pull issued behind it (vmcnt(49)).
+// colM[(tile * 16 + g / 2) * 128 + 2 lane + (g & 1)] = -col_ring[4 g + lane / 16][16 tile + lane % 16], g = 0..31 (16 KiB per tile);
+// zeroes the nctr ticket counters (128 bytes apart)
+__global__ __launch_bounds__(256) void k_pack_multipliers_mfma128(const double* __restrict__ col_ring, int64_t mp,
+                                                                  const LpxCtl* __restrict__ ring, int kmax, int ntiles,
+                                                                  double* __restrict__ colM, unsigned* __restrict__ tickets, int nctr,
+                                                                  long long* __restrict__ clk) {
+  __shared__ int sh_np;
+  const int np = ring_count128(ring, kmax, &sh_np);
+  if (blockIdx.x == 0)
+    for (int u = threadIdx.x; u < nctr; u += 256) tickets[u * 32] = 0u;
+  // the clock probe: k_sweep128_mfma takes no stamps, so the words of an earlier pulled sweep are cleared here (in a loop
+  // call the blocks of more than 64 come first: no stamped sweep of the same call is in flight beside this launch) and
+  // lpx_state_info.sweep_clock_mhz says 0 — without a memset packet between the sweeps
+  if (clk && blockIdx.x == 0 && threadIdx.x < 32) clk[threadIdx.x] = 0;
+  const int tile = blockIdx.x;
+  if (tile >= ntiles) return;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int idx = q * 256 + threadIdx.x;          // 0 .. 2047 = 32 groups x 64 lanes
+    const int g = idx >> 6, l = idx & 63, k = l >> 4, i = l & 15;
+    const int s = 4 * g + k;
+    const double c = s < np ? col_ring[(int64_t)s * mp + (int64_t)tile * 16 + i] : 0.0;
+    colM[(int64_t)tile * 2048 + (g >> 1) * 128 + 2 * l + (g & 1)] = -c;
+  }
+}
+#define LPX_MFMA_FENCE __builtin_amdgcn_sched_barrier(0)
+template <bool NT, bool OOP>
+__global__ __launch_bounds__(256, 2) void k_sweep128_mfma(double* A, const double* Asrc,   // (no __restrict__, as k_sweep64_mfma2)
+                                                          int64_t ld, int m_local,
+                                                          const double* __restrict__ prow_ring,
+                                                          const LpxCtl* __restrict__ ring, int kmax, int nsub,
+                                                          const double* colM,   // [tile][pair of groups][lane][2]
+                                                          unsigned* tickets, int nranges) {
+  constexpr int NG = 32, CT = 4;
+  constexpr int kRsrcWord3 = 0x00020000;           // raw buffer, 32-bit data format (gfx9 family)
+  constexpr int kAuxNt = NT ? 2 : 0;               // cache policy bit 1 = nt
+  __shared__ __attribute__((aligned(16))) double sh_b[NG * CT * 64];   // 64 KiB: [group][column tile][lane]
+  __shared__ int sh_np, sh_chunk;
+  const int np = ring_count128(ring, kmax, &sh_np);
+  // no valid pivot (the block behind the one in which the LP ended): in place nothing to do; out of place the tableau still
+  // has to be carried over — every step an identity step (multiplier -0.0 against a pivot-row value of +0.0: exact)
+  if (np < 1 && !OOP) return;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int rowblocks = m_local / 16;
+  const int per_range = (rowblocks + nranges - 1) / nranges;
+  const int nchunks = nsub * nranges;
+  const int64_t row_bytes = ld * 8;
+  const uint32_t rb32 = (uint32_t)row_bytes;       // 16 rows x ld x 8 < 2^32 (launcher)
+  const uint32_t off_c = (uint32_t)(lane >> 4) * rb32 + (uint32_t)(lane & 15) * 8u;   // row lane / 16, column lane % 16
+  const uint32_t off_a = (uint32_t)lane * 8u;
+  int sub_loaded = -1;
+  for (;;) {
+    if (threadIdx.x == 0) sh_chunk = (int)atomicAdd(tickets, 1u);
+    __syncthreads();
+    const int chunk = __builtin_amdgcn_readfirstlane(sh_chunk);
+    if (chunk >= nchunks) return;
+    const int sub = chunk % nsub, range = chunk / nsub;
+    const int rb0 = range * per_range;
+    const int ntiles = min(rowblocks, rb0 + per_range) - rb0;   // 16-row tiles of this chunk
+    if (sub != sub_loaded) {   // uniform
+      for (int q = wave; q < NG * CT; q += 4) {
+        const int g = q / CT, ct = q % CT;
+        const int s = 4 * g + (lane >> 4);
+        sh_b[q * 64 + lane] = s < np ? prow_ring[(int64_t)s * ld + sub * 64 + ct * 16 + (lane & 15)] : 0.0;
+      }
+      sub_loaded = sub;
+    }
+    __syncthreads();
+    if (ntiles > 0) {
+      unsigned* const ctr = tickets + 32 * (1 + chunk);
+      char* const dst_base = reinterpret_cast<char*>(A + sub * 64) + (int64_t)rb0 * 16 * row_bytes;
+      const char* const src_base = OOP ? reinterpret_cast<const char*>(Asrc + sub * 64) + (int64_t)rb0 * 16 * row_bytes : dst_base;
+      const double* const colM0 = colM + (int64_t)rb0 * 2048;
+      auto load_tile = [&](int t, d4v (&c)[CT], double (&a)[NG]) {
+        const int tt = max(0, min(t, ntiles - 1));                          // uniform; past the end: the last tile again
+        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<char*>(src_base) + (int64_t)tt * 16 * row_bytes, 0, -1, kRsrcWord3);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int ct = 0; ct < CT; ++ct)
+            c[ct][r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rc, off_c + (uint32_t)ct * 128u,
+                                                                                         (int)((uint32_t)(4 * r) * rb32), kAuxNt));
+        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<double*>(colM0) + (int64_t)tt * 2048, 0, -1, kRsrcWord3);
+#pragma unroll
+        for (int p = 0; p < NG / 2; ++p) {   // pairs: the A operands of groups 2 p and 2 p + 1 side by side, 1 KiB per pair
+          const v4u x = __builtin_amdgcn_raw_buffer_load_b128(ra, 2u * off_a + (uint32_t)(p & 3) * 1024u, (p >> 2) * 4096, 0);
+          a[2 * p] = __builtin_bit_cast(double, v2u{x[0], x[1]});
+          a[2 * p + 1] = __builtin_bit_cast(double, v2u{x[2], x[3]});
+        }
+      };
+      auto work_tile = [&](int t, d4v (&c)[CT], const double (&a)[NG]) {
+        const double* const bl = sh_b + lane;
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+          for (int ct = 0; ct < CT; ++ct)
+            c[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[g], bl[(g * CT + ct) * 64], c[ct], 0, 0, 0);
+        // the B operands of group g + 1 (two ds_read2st64_b64) are asked for in front of group g's four MFMAs
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          if (g + 1 < NG) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+        }
+        // a ticket past the end: the arithmetic runs on the re-read last tile and the stores are DROPPED by the buffer's range check
+        const int tt = max(0, min(t, ntiles - 1));
+        char* const out = dst_base + (int64_t)tt * 16 * row_bytes;
+        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(out, 0, __builtin_amdgcn_readfirstlane((unsigned)t < (unsigned)ntiles ? -1 : 0), kRsrcWord3);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int ct = 0; ct < CT; ++ct)
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, (double)c[ct][r]), rd, off_c + (uint32_t)ct * 128u,
+                                                  (int)((uint32_t)(4 * r) * rb32), kAuxNt);
+      };
+      constexpr int kStepOps = 16 + 16 + 16;   // a step's C loads, A loads and stores
+      auto take = [&](unsigned& tk) -> int {
+        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kStepOps + 1) : "memory");
+        return ticket_take(tk);
+      };
+      d4v c0[CT], c1[CT];
+      double a0[NG], a1[NG];
+      unsigned ka, kb = 0;
+      ticket_pull(ka, ctr);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      int t0 = ticket_take(ka);
+      if (t0 < ntiles) {   // uniform
+        load_tile(t0, c0, a0);
+        ticket_pull(ka, ctr);                 // the ticket of the tile the loop's first step loads
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the loop is entered with nothing in flight (see k_sweep64_mfma2)
+#pragma unroll 1
+        do {
+          ticket_pull(kb, ctr);
+          const int t1 = take(ka);
+          load_tile(t1, c1, a1);
+          LPX_MFMA_FENCE;
+          work_tile(t0, c0, a0);
+          LPX_MFMA_FENCE;
+          ticket_pull(ka, ctr);
+          const int t2 = take(kb);
+          load_tile(t2, c0, a0);
+          LPX_MFMA_FENCE;
+          work_tile(t1, c1, a1);
+          LPX_MFMA_FENCE;
+          t0 = t2;
+        } while (t0 < ntiles);
+      }
+      // the last pull's return (and the re-read tile) must have landed before the registers are used again
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("" : "+v"(ka), "+v"(kb) :: "memory");
+    }
+    __syncthreads();   // every wave is through with sh_b and sh_chunk
+  }
+}
+#undef LPX_MFMA_FENCE
 #ifdef LPX_WITH_VARIANTS
 #define LPX_VARIANT_PART 7
 #include "variants/lpx_variants.inc"
@@ -1154,14 +1344,18 @@ __device__ __forceinline__ double apply_pivot(double v, int i, int j, int l_r, i
 constexpr int kFixChunk = 8;
 // The chains of a job: the LAST pending pivot of every distinct key (entering slot / leaving row), in pivot order.  Called
 // by the first wave of a workgroup (all 64 lanes) between two barriers; keys[q] = -1 behind the last pivot.
+// (up to kBlockMax = 128 pending pivots: lane q looks after pivots q and 64 + q)
 __device__ __forceinline__ void fix_pick_chains(const int* keys, int np, int* sh_pick, int* sh_npick) {
   const int q = threadIdx.x;
-  const int key = keys[q];
-  bool keep = q < np;
+  const int key = keys[q], key_hi = keys[64 + q];
+  bool keep = q < np, keep_hi = 64 + q < np;
   for (int r = q + 1; r < np; ++r) keep = keep && keys[r] != key;
-  const unsigned long long mask = __ballot(keep);
-  if (keep) sh_pick[__popcll(mask & ((1ull << q) - 1ull))] = q;
-  const int npick = __popcll(mask);
+  for (int r = 64 + q + 1; r < np; ++r) keep_hi = keep_hi && keys[r] != key_hi;
+  const unsigned long long mask = __ballot(keep), mask_hi = __ballot(keep_hi);
+  const unsigned long long below = (1ull << q) - 1ull;
+  if (keep) sh_pick[__popcll(mask & below)] = q;
+  if (keep_hi) sh_pick[__popcll(mask) + __popcll(mask_hi & below)] = 64 + q;
+  const int npick = __popcll(mask) + __popcll(mask_hi);
   if (q < kFixChunk) sh_pick[npick + q] = 0;   // (padding of the last chunk: reads stay inside the ring)
   if (q == 0) *sh_npick = npick;
 }
@@ -1176,7 +1370,7 @@ __global__ __launch_bounds__(256) void k_block_fixup(double* __restrict__ A, int
   // img_col / img_row != NULL (the overlapped loop): the chains are computed BESIDE the block's sweep, from ring values
   // only, into compact images [chain][row] / [chain][column]; k_block_fixup_scatter copies them into the tableau once the
   // sweep is through.  b (job 2) is written in place either way: the sweep does not touch it.
-  static_assert(kBlockMax <= 64, "one lane per pending pivot in the hit ballots");
+  static_assert(kBlockMax == 128, "two words of hit ballots: lane u asks for pending pivots u and 64 + u");
   if (clk && blockIdx.x < 8 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) {
     const unsigned x = xcc_id() & 7u;
     clk[x * 4 + 2] = __builtin_amdgcn_s_memtime(); clk[x * 4 + 3] = wall_clock64();
@@ -1188,7 +1382,7 @@ __global__ __launch_bounds__(256) void k_block_fixup(double* __restrict__ A, int
   const int s0 = blockIdx.y * kFixChunk, job = blockIdx.z;
   // (the grid is max(m, ld) wide for all three jobs: a workgroup with nothing to do leaves before the ring is looked at)
   if ((int64_t)blockIdx.x * blockDim.x >= (job == 1 ? ld : (int64_t)m_local) || (job == 2 && s0 != 0)) return;
-  const int np = ring_count(ring, kBlockMax, kmax, &sh_np);
+  const int np = ring_count128(ring, kmax, &sh_np);
   if (job == 2 ? s0 != 0 : s0 >= np) return;  // the b job also runs for an empty block (out of place: it copies b)
   if ((int)threadIdx.x < kBlockMax) {   // (slots behind the last pivot: -1, matches nothing)
     const bool live = (int)threadIdx.x < np;
@@ -1228,6 +1422,7 @@ __global__ __launch_bounds__(256) void k_block_fixup(double* __restrict__ A, int
     __syncthreads();
     // pivots whose own row is one of this wave's 64 rows (all lanes active here: lane r asks for pivot r)
     const unsigned long long hit = __ballot((unsigned)(sh_l[lane] - t_wave) < 64u);
+    const unsigned long long hit_hi = __ballot((unsigned)(sh_l[64 + lane] - t_wave) < 64u);
     if (t < m_local) {
       double v[kFixChunk];
 #pragma unroll
@@ -1248,7 +1443,7 @@ __global__ __launch_bounds__(256) void k_block_fixup(double* __restrict__ A, int
 #pragma unroll
             for (int q = 0; q < kFixChunk; ++q) x[q] = sh_x[r][q];
             const int eq = __builtin_amdgcn_readfirstlane(sh_eq[r]);
-            if (eq == 0 && !((hit >> r) & 1)) {   // (uniform, the common case) eight plain steps
+            if (eq == 0 && !(((r < 64 ? hit >> r : hit_hi >> (r - 64))) & 1)) {   // (uniform, the common case) eight plain steps
 #pragma unroll
               for (int q = 0; q < kFixChunk; ++q) v[q] = submul(v[q], cv[u], x[q]);                    // :162
             } else {
@@ -1288,6 +1483,7 @@ __global__ __launch_bounds__(256) void k_block_fixup(double* __restrict__ A, int
     __syncthreads();
     // pivots that entered at one of this wave's 64 slots (the division of :157 sits in THAT column)
     const unsigned long long hit = __ballot((unsigned)(sh_e[lane] - t_wave) < 64u);
+    const unsigned long long hit_hi = __ballot((unsigned)(sh_e[64 + lane] - t_wave) < 64u);
     if (t < (int)ld) {
       double v[kFixChunk];
 #pragma unroll
@@ -1306,7 +1502,7 @@ __global__ __launch_bounds__(256) void k_block_fixup(double* __restrict__ A, int
 #pragma unroll
             for (int q = 0; q < kFixChunk; ++q) x[q] = sh_x[r][q];
             const int eq = __builtin_amdgcn_readfirstlane(sh_eq[r]);
-            if (eq == 0 && !((hit >> r) & 1)) {
+            if (eq == 0 && !(((r < 64 ? hit >> r : hit_hi >> (r - 64))) & 1)) {
 #pragma unroll
               for (int q = 0; q < kFixChunk; ++q) v[q] = submul(v[q], x[q], pv[u]);
             } else {
@@ -1336,6 +1532,7 @@ __global__ __launch_bounds__(256) void k_block_fixup(double* __restrict__ A, int
     }
   } else {  // b of every local row (LPState.java:164 / :146)
     const unsigned long long hit = __ballot((unsigned)(sh_l[lane] - t_wave) < 64u);
+    const unsigned long long hit_hi = __ballot((unsigned)(sh_l[64 + lane] - t_wave) < 64u);
     if (t < m_local) {
       double bi = b_src[t];  // == b unless the sweep ran out of place
       for (int r0 = 0; r0 < np; r0 += 8) {
@@ -1348,7 +1545,7 @@ __global__ __launch_bounds__(256) void k_block_fixup(double* __restrict__ A, int
           if (r < np) {
             const double nb = submul(bi, cv[q], sh_bl[r]);
             bi = nb;
-            if ((hit >> r) & 1) { if (t == sh_l[r]) bi = sh_bl[r]; }
+            if ((r < 64 ? hit >> r : hit_hi >> (r - 64)) & 1) { if (t == sh_l[r]) bi = sh_bl[r]; }
           }
         }
       }
@@ -1372,7 +1569,7 @@ __global__ __launch_bounds__(256) void k_block_fixup_scatter(double* __restrict_
   __shared__ int sh_np, sh_npick;
   const int s0 = blockIdx.y * kFixChunk, job = blockIdx.z;
   if ((int64_t)blockIdx.x * blockDim.x >= (job == 1 ? ld : (int64_t)m_local)) return;
-  const int np = ring_count(ring, kBlockMax, kmax, &sh_np);
+  const int np = ring_count128(ring, kmax, &sh_np);
   if (s0 >= np) return;
   if ((int)threadIdx.x < kBlockMax) {
     const bool live = (int)threadIdx.x < np;

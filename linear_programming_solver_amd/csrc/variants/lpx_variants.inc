@@ -1118,182 +1118,6 @@ __global__ __launch_bounds__(256, 2) void k_sweep64_mfma2_diag(double* A, const 
 }
 
 #undef LPX_MFMA_FENCE
-// ---- k_sweep128_mfma: a block of up to 128 pivots per pass (EXPERIMENTS 000.55; written at the end of round 5, NOT yet run on a
-// GPU when committed — scripts/micro/sweep_mfma128.hip compares it bit for bit with two passes of k_sweep64_mfma2).
-// Twice the arithmetic per memory pass puts the kernel at the matrix pipe's floor (the projection: 2.63 ms per 128 pivots on 192
-// CUs).  What changes against k_sweep64_mfma2:
-//  * the B operands of 128 pivots take 64 KiB for ONE 64-column sub-strip: a workgroup (four waves, two workgroups per CU as
-//    before) is bound to a sub-strip, not to a 128-column group;
-//  * 256 sub-strips at n = 16384 do not divide 2 x 192 resident workgroups, so the binding is not static: a workgroup pulls
-//    CHUNKS (sub-strip, row range) from tickets[0] — chunks of one row range are adjacent sub-strips, so the workgroups running
-//    side by side still cover whole rows —, loads the sub-strip's B operands if it changed, and its waves pull the chunk's
-//    16-row tiles from the chunk's own counter (tickets[32 * (1 + chunk)]);
-//  * two tile buffers instead of three (a tile's A operands are 32 doubles per lane: c 2 x 32 + a 2 x 64 VGPRs): the arithmetic of a
-//    tile is twice as long, one tile ahead is as much time as two were;
-//  * a ticket is pulled a step before it is taken, as there: the wait in front of the take covers the 32 loads, 16 stores and
-//    the next pull issued behind it (vmcnt(49)).
-__device__ __forceinline__ int ring_count128(const LpxCtl* __restrict__ ring, int kmax, int* sh_np) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    const unsigned long long m0 = __ballot(lane < kmax && ring[lane].do_update != 0);
-    const unsigned long long m1 = __ballot(lane + 64 < kmax && ring[lane + 64].do_update != 0);
-    const int n0 = (~m0 == 0ull) ? 64 : (__ffsll((long long)~m0) - 1);
-    const int n1 = (~m1 == 0ull) ? 64 : (__ffsll((long long)~m1) - 1);
-    if (lane == 0) *sh_np = n0 < 64 ? n0 : 64 + n1;
-  }
-  __syncthreads();
-  return *sh_np;
-}
-// colM[(tile * 16 + g / 2) * 128 + 2 lane + (g & 1)] = -col_ring[4 g + lane / 16][16 tile + lane % 16], g = 0..31 (16 KiB per tile);
-// zeroes the nctr ticket counters (128 bytes apart)
-__global__ __launch_bounds__(256) void k_pack_multipliers_mfma128(const double* __restrict__ col_ring, int64_t mp,
-                                                                  const LpxCtl* __restrict__ ring, int kmax, int ntiles,
-                                                                  double* __restrict__ colM, unsigned* __restrict__ tickets, int nctr) {
-  __shared__ int sh_np;
-  const int np = ring_count128(ring, kmax, &sh_np);
-  if (blockIdx.x == 0)
-    for (int u = threadIdx.x; u < nctr; u += 256) tickets[u * 32] = 0u;
-  const int tile = blockIdx.x;
-  if (tile >= ntiles) return;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const int idx = q * 256 + threadIdx.x;          // 0 .. 2047 = 32 groups x 64 lanes
-    const int g = idx >> 6, l = idx & 63, k = l >> 4, i = l & 15;
-    const int s = 4 * g + k;
-    const double c = s < np ? col_ring[(int64_t)s * mp + (int64_t)tile * 16 + i] : 0.0;
-    colM[(int64_t)tile * 2048 + (g >> 1) * 128 + 2 * l + (g & 1)] = -c;
-  }
-}
-#define LPX_MFMA_FENCE __builtin_amdgcn_sched_barrier(0)
-template <bool NT, bool OOP>
-__global__ __launch_bounds__(256, 2) void k_sweep128_mfma(double* A, const double* Asrc,   // (no __restrict__, as k_sweep64_mfma2)
-                                                          int64_t ld, int m_local,
-                                                          const double* __restrict__ prow_ring,
-                                                          const LpxCtl* __restrict__ ring, int kmax, int nsub,
-                                                          const double* colM,   // [tile][pair of groups][lane][2]
-                                                          unsigned* tickets, int nranges) {
-  constexpr int NG = 32, CT = 4;
-  constexpr int kRsrcWord3 = 0x00020000;           // raw buffer, 32-bit data format (gfx9 family)
-  constexpr int kAuxNt = NT ? 2 : 0;               // cache policy bit 1 = nt
-  __shared__ __attribute__((aligned(16))) double sh_b[NG * CT * 64];   // 64 KiB: [group][column tile][lane]
-  __shared__ int sh_np, sh_chunk;
-  const int np = ring_count128(ring, kmax, &sh_np);
-  if (np < 1) return;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int rowblocks = m_local / 16;
-  const int per_range = (rowblocks + nranges - 1) / nranges;
-  const int nchunks = nsub * nranges;
-  const int64_t row_bytes = ld * 8;
-  const uint32_t rb32 = (uint32_t)row_bytes;       // 16 rows x ld x 8 < 2^32 (launcher)
-  const uint32_t off_c = (uint32_t)(lane >> 4) * rb32 + (uint32_t)(lane & 15) * 8u;   // row lane / 16, column lane % 16
-  const uint32_t off_a = (uint32_t)lane * 8u;
-  int sub_loaded = -1;
-  for (;;) {
-    if (threadIdx.x == 0) sh_chunk = (int)atomicAdd(tickets, 1u);
-    __syncthreads();
-    const int chunk = __builtin_amdgcn_readfirstlane(sh_chunk);
-    if (chunk >= nchunks) return;
-    const int sub = chunk % nsub, range = chunk / nsub;
-    const int rb0 = range * per_range;
-    const int ntiles = min(rowblocks, rb0 + per_range) - rb0;   // 16-row tiles of this chunk
-    if (sub != sub_loaded) {   // uniform
-      for (int q = wave; q < NG * CT; q += 4) {
-        const int g = q / CT, ct = q % CT;
-        const int s = 4 * g + (lane >> 4);
-        sh_b[q * 64 + lane] = s < np ? prow_ring[(int64_t)s * ld + sub * 64 + ct * 16 + (lane & 15)] : 0.0;
-      }
-      sub_loaded = sub;
-    }
-    __syncthreads();
-    if (ntiles > 0) {
-      unsigned* const ctr = tickets + 32 * (1 + chunk);
-      char* const dst_base = reinterpret_cast<char*>(A + sub * 64) + (int64_t)rb0 * 16 * row_bytes;
-      const char* const src_base = OOP ? reinterpret_cast<const char*>(Asrc + sub * 64) + (int64_t)rb0 * 16 * row_bytes : dst_base;
-      const double* const colM0 = colM + (int64_t)rb0 * 2048;
-      auto load_tile = [&](int t, d4v (&c)[CT], double (&a)[NG]) {
-        const int tt = max(0, min(t, ntiles - 1));                          // uniform; past the end: the last tile again
-        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char*>(src_base) + (int64_t)tt * 16 * row_bytes, 0, -1, kRsrcWord3);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int ct = 0; ct < CT; ++ct)
-            c[ct][r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rc, off_c + (uint32_t)ct * 128u,
-                                                                                         (int)((uint32_t)(4 * r) * rb32), kAuxNt));
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<double*>(colM0) + (int64_t)tt * 2048, 0, -1, kRsrcWord3);
-#pragma unroll
-        for (int p = 0; p < NG / 2; ++p) {   // pairs: the A operands of groups 2 p and 2 p + 1 side by side, 1 KiB per pair
-          const v4u x = __builtin_amdgcn_raw_buffer_load_b128(ra, 2u * off_a + (uint32_t)(p & 3) * 1024u, (p >> 2) * 4096, 0);
-          a[2 * p] = __builtin_bit_cast(double, v2u{x[0], x[1]});
-          a[2 * p + 1] = __builtin_bit_cast(double, v2u{x[2], x[3]});
-        }
-      };
-      auto work_tile = [&](int t, d4v (&c)[CT], const double (&a)[NG]) {
-        const double* const bl = sh_b + lane;
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-#pragma unroll
-          for (int ct = 0; ct < CT; ++ct)
-            c[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[g], bl[(g * CT + ct) * 64], c[ct], 0, 0, 0);
-        // the B operands of group g + 1 (two ds_read2st64_b64) are asked for in front of group g's four MFMAs
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-          if (g + 1 < NG) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-        }
-        // a ticket past the end: the arithmetic runs on the re-read last tile and the stores are DROPPED by the buffer's range check
-        const int tt = max(0, min(t, ntiles - 1));
-        char* const out = dst_base + (int64_t)tt * 16 * row_bytes;
-        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(out, 0, __builtin_amdgcn_readfirstlane((unsigned)t < (unsigned)ntiles ? -1 : 0), kRsrcWord3);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int ct = 0; ct < CT; ++ct)
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, (double)c[ct][r]), rd, off_c + (uint32_t)ct * 128u,
-                                                  (int)((uint32_t)(4 * r) * rb32), kAuxNt);
-      };
-      constexpr int kStepOps = 16 + 16 + 16;   // a step's C loads, A loads and stores
-      auto take = [&](unsigned& tk) -> int {
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kStepOps + 1) : "memory");
-        return ticket_take(tk);
-      };
-      d4v c0[CT], c1[CT];
-      double a0[NG], a1[NG];
-      unsigned ka, kb = 0;
-      ticket_pull(ka, ctr);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      int t0 = ticket_take(ka);
-      if (t0 < ntiles) {   // uniform
-        load_tile(t0, c0, a0);
-        ticket_pull(ka, ctr);                 // the ticket of the tile the loop's first step loads
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the loop is entered with nothing in flight (see k_sweep64_mfma2)
-#pragma unroll 1
-        do {
-          ticket_pull(kb, ctr);
-          const int t1 = take(ka);
-          load_tile(t1, c1, a1);
-          LPX_MFMA_FENCE;
-          work_tile(t0, c0, a0);
-          LPX_MFMA_FENCE;
-          ticket_pull(ka, ctr);
-          const int t2 = take(kb);
-          load_tile(t2, c0, a0);
-          LPX_MFMA_FENCE;
-          work_tile(t1, c1, a1);
-          LPX_MFMA_FENCE;
-          t0 = t2;
-        } while (t0 < ntiles);
-      }
-      // the last pull's return (and the re-read tile) must have landed before the registers are used again
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("" : "+v"(ka), "+v"(kb) :: "memory");
-    }
-    __syncthreads();   // every wave is through with sh_b and sh_chunk
-  }
-}
-#undef LPX_MFMA_FENCE
+// (k_sweep128_mfma and k_pack_multipliers_mfma128, first written here, are the product's: lpx_sweeps.inc)
 #endif  // part 7
 

@@ -47,7 +47,7 @@ class LPState:
             if rc:
                 raise_for_status(rc)
 
-        if block is not None:          # pivots per sweep of the device loop: None/0 = by size, 1 = off, 2..64
+        if block is not None:          # pivots per sweep of the device loop: None/0 = by size, 1 = off, 2..128
             rc = L.lpx_state_set_block(h, int(block))
             if rc:
                 raise_for_status(rc)
@@ -178,9 +178,9 @@ class LPState:
     def chain_trace(self):
         """Phase timestamps (100 MHz ticks) of the last decision launch: array [decisions, 5]; needs option
         chain_trace = 1 before the loop."""
-        buf = np.zeros(5 * 64, dtype=np.int64)
+        buf = np.zeros(5 * 128, dtype=np.int64)
         nd = C.c_int32()
-        rc = self._L.lpx_state_read_chain_trace(self._h, buf.ctypes.data_as(_lib.i64p), 64, C.byref(nd))
+        rc = self._L.lpx_state_read_chain_trace(self._h, buf.ctypes.data_as(_lib.i64p), 128, C.byref(nd))
         if rc:
             raise_for_status(rc)
         return buf[: 5 * nd.value].reshape(nd.value, 5)
@@ -189,9 +189,9 @@ class LPState:
         """Every stamp the decision kernel keeps: array [decisions, 8] for k_block_chain2 (option chain_form = 1: start,
         phase A's loads arrived, candidate published, every candidate read, phase B's loads arrived, hand-off stored,
         phase B done, next entering slot known), [decisions, 5] otherwise."""
-        buf = np.zeros(16 * 64, dtype=np.int64)
+        buf = np.zeros(16 * 128, dtype=np.int64)
         nd, ns = C.c_int32(), C.c_int32()
-        rc = self._L.lpx_state_read_chain_trace_fine(self._h, buf.ctypes.data_as(_lib.i64p), 64, C.byref(nd), C.byref(ns))
+        rc = self._L.lpx_state_read_chain_trace_fine(self._h, buf.ctypes.data_as(_lib.i64p), 128, C.byref(nd), C.byref(ns))
         if rc:
             raise_for_status(rc)
         return buf[: ns.value * nd.value].reshape(nd.value, ns.value)

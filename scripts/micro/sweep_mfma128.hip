@@ -1,4 +1,4 @@
-// k_sweep128_mfma (csrc/variants/: a block of up to 128 pivots per pass on the matrix cores, EXPERIMENTS 000.55) alone on a
+// k_sweep128_mfma (lpx_sweeps.inc: a block of up to 128 pivots per pass on the matrix cores, EXPERIMENTS 000.55) alone on a
 // synthetic ring, out of place, against TWO passes of the product's k_sweep64_mfma2 (pivots 0..63 out of place, 64..127 in
 // place on the result): time and a bit-for-bit comparison of every entry, for full and partly filled blocks.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DLPX_FUSED=1 -DLPX_WITH_VARIANTS
@@ -107,7 +107,7 @@ int main(int argc, char** argv) {
     };
     auto one_pass = [&] {
       hipLaunchKernelGGL(k_pack_multipliers_mfma128, dim3(rowblocks), dim3(256), 0, st, (const double*)col, mp, (const LpxCtl*)up, KT,
-                         rowblocks, col_packed128, tickets128, nchunks + 1);
+                         rowblocks, col_packed128, tickets128, nchunks + 1, (long long*)nullptr);
       hipLaunchKernelGGL((k_sweep128_mfma<true, true>), dim3(2 * cus), dim3(256), 0, st, dst, (const double*)src, ld, m,
                          (const double*)prow, (const LpxCtl*)up, KT, nsub, (const double*)col_packed128, tickets128, nranges);
     };
