@@ -28,10 +28,11 @@ def oracle(arith):
     return ArithOracle(pyoracle, arith)
 
 
-def _loops_vs_oracle(lps, oracle, A, b, c, budgets, what, pricing=None, after=None, **kw):
-    """Resumed loop calls with block = 128 against the oracle: status, pivots and every bit of the state after each call.
-    after(k, st): a look at the handle behind call k."""
-    st = lps.LPState(A, b, c, block=128, **dict(kw, **({"pricing": pricing} if pricing else {})))
+def _loops_vs_oracle(lps, oracle, A, b, c, budgets, what, pricing=None, after=None, block=128, want_block=None, **kw):
+    """Resumed loop calls with block = 128 (or `block`) against the oracle: status, pivots and every bit of the state after
+    each call.  after(k, st): a look at the handle behind call k, while the LP is still running.  want_block: what
+    lpx_state_info.block must say in the end where an option clamps the block."""
+    st = lps.LPState(A, b, c, block=block, **dict(kw, **({"pricing": pricing} if pricing else {})))
     ref = oracle.State(A, b, c, kind=oracle.FP64, pricing=1 if pricing == "dantzig" else 0)
     status = None
     for k, budget in enumerate(budgets):
@@ -43,7 +44,7 @@ def _loops_vs_oracle(lps, oracle, A, b, c, budgets, what, pricing=None, after=No
             after(k, st)
         if status != 9:
             break
-    assert st.info()["block"] == 128, st.info()
+    assert st.info()["block"] == (block if want_block is None else want_block), st.info()
     st.close()
     ref.close()
     return status
@@ -80,15 +81,27 @@ def test_blocks_of_128_on_ragged_shapes(lps, oracle, shape):
     _loops_vs_oracle(lps, oracle, A, b, c, (127, 2 * 128 + 5, 127, 300), "128 on %s" % (shape,), after=after)
 
 
-@pytest.mark.parametrize("shape", [(600, 900), (1536, 700)])
+@pytest.mark.parametrize("shape", [(600, 900), (1536, 700), (1024, 2048)])
 @pytest.mark.parametrize("pricing", ["dantzig", None])
 def test_blocks_of_128_with_long_ladders(lps, oracle, shape, pricing):
     """Dantzig pricing seldom returns to a slot, so a decision's ladder runs through up to 256 pending pivots: all four
     windows of eight chunks, and the boundary value between the two blocks' pivots in each of them.  Both rules, budgets
-    that are no multiples of 128 (the counterpart of test_blocks_of_64_with_long_ladders)."""
+    that are no multiples of 128 (the counterpart of test_blocks_of_64_with_long_ladders).  The first two shapes are ragged
+    and take the generic passes; 1024 x 2048 has whole strips of 16-row tiles: the long ladders in front of k_sweep128_mfma
+    in the fused mode.  That LP is still running after all four budgets under either rule."""
     m, n = shape
     A, b, c = dense_lp(m, n, seed=m + 7 * n)
-    _loops_vs_oracle(lps, oracle, A, b, c, (200, 333, 129, 257), "%s on %s" % (pricing, shape), pricing=pricing)
+    whole = m % 16 == 0 and n % 512 == 0
+    name = "k_sweep128_mfma" if (oracle.mode == "fused" and whole) else "k_update_multi"
+
+    def after(k, st):
+        if k in (0, 1):   # the call's last sweep took 73 / 78 decisions (201 = 128 + 73, 334 = 2 x 128 + 78)
+            assert st.info()["sweep_kernel_name"] == name, st.info()
+
+    status = _loops_vs_oracle(lps, oracle, A, b, c, (200, 333, 129, 257), "%s on %s" % (pricing, shape), pricing=pricing,
+                              after=after)
+    if whole:
+        assert status == 9
 
 
 def test_blocks_of_128_with_two_rows_per_thread(lps, oracle):
