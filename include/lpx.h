@@ -517,6 +517,44 @@ int lpx_solve_scenarios(int32_t m, int32_t n, const double* A, int64_t lda, int3
                         const double* c, int64_t ldc, const int32_t* maximize, const lpx_solve_options* opts,
                         lpx_solve_result* results, double* x_out, int32_t* perm_out);
 
+/* Re-solve from a shared basis.  A scenario sweep is a base case plus perturbations; the base case's optimal basis is
+ * optimal or nearly so for most of them.  lpx_scenarios_set_basis brings the handle's matrix to such a basis ONCE;
+ * lpx_scenarios_resolve then brings each scenario's (b, c) to it in O(m + n) per crash pivot and, decided on chip, takes
+ *   LPX_ROUTE_PRIMAL  b' >= 0 at the basis: the primal loop from there
+ *   LPX_ROUTE_DUAL    some b' < 0 and no c'[j] > 1e-9: a dual simplex loop (leaving row by minInB on b' while it finds an
+ *                     entry below -1e-9; entering slot by the smallest c'[j] / A'[l][j] over A'[l][j] < -1e-9, lowest slot
+ *                     on ties; none: LPX_INFEASIBLE), then the primal loop, which normally ends at once.  Phase 1 and its
+ *                     restore are never entered
+ *   LPX_ROUTE_COLD    neither: the scenario is solved exactly as lpx_scenarios_solve solves it
+ * Every pivot is the reference's pivot (LPState.java:133-181) in the handle's arithmetic mode. */
+#define LPX_ROUTE_COLD 0
+#define LPX_ROUTE_PRIMAL 1
+#define LPX_ROUTE_DUAL 2
+/* `basis`: the m variable ids that are to be basic, in perm's numbering (0..n-1 the original variables, n..n+m-1 the
+ * slacks; the perm[n:] a solve returned will do), in any order; NULL clears the handle's basis.  An entry outside
+ * [0, n + m) or a repeated one gives LPX_BAD_ARGUMENT naming the entry, before any device call.  One workgroup then makes
+ * one pass over the slots: where a wanted variable is nonbasic it pivots on the largest |A[i][slot]| among the rows whose
+ * basic variable is not wanted (lowest row on ties); none, or a largest <= 1e-9: LPX_BAD_ARGUMENT "basis is singular at
+ * variable id ...", and the handle is left without a basis.  crash_pivots_out (may be NULL): the pivots that took; they
+ * are never counted in a result.  Calling it again replaces the basis; changing LPX_OPT_FUSED clears it.
+ * lpx_scenarios_solve never looks at the basis. */
+int lpx_scenarios_set_basis(lpx_scenarios* s, const int32_t* basis, int32_t* crash_pivots_out);
+/* lpx_scenarios_solve from the handle's basis (none: LPX_BAD_ARGUMENT); arguments and their checks as there.  route_out
+ * (may be NULL) is int32[count]: LPX_ROUTE_*.  A scenario routed primal or dual has phase1_used = 0, x0_slot = -1,
+ * pivots_phase1 = the pivots of the dual loop (0 on the primal route), pivots_phase2 = those of the primal loop, max_pivots
+ * being the budget of both together, and objective etc. from its final state; that state is always m x n, so its rows of
+ * x_out and perm_out are written whatever its status.  A scenario routed cold has exactly what lpx_scenarios_solve fills
+ * for it, rows included; restore_order only matters there. */
+int lpx_scenarios_resolve(lpx_scenarios* s, int32_t count, const double* b, int64_t ldb, const double* c, int64_t ldc,
+                          const int32_t* maximize, int64_t max_pivots, const int32_t* restore_order, int32_t restore_order_len,
+                          lpx_solve_result* results, double* x_out, int32_t* perm_out, int32_t* route_out);
+/* lpx_scenarios_create, lpx_scenarios_set_basis, lpx_scenarios_resolve, lpx_scenarios_destroy; options as
+ * lpx_solve_scenarios.  basis must not be NULL.  All argument checks of the three steps come before the first device call. */
+int lpx_solve_scenarios_from_basis(int32_t m, int32_t n, const double* A, int64_t lda, const int32_t* basis, int32_t count,
+                                   const double* b, int64_t ldb, const double* c, int64_t ldc, const int32_t* maximize,
+                                   const lpx_solve_options* opts, lpx_solve_result* results, double* x_out, int32_t* perm_out,
+                                   int32_t* route_out);
+
 /* LPState restoreInitialLP(auxLP, initial, indexOfX0)                   LPSolver.java:200-246
  * In place on the auxiliary-LP handle (m x (n+1), as left by phase 1): drops x0's column, rebuilds c and v by
  * substitution in keySet() order (`order`, order_len <= n original-variable indices; NULL = default-name order of all n), renumbers

@@ -12,6 +12,7 @@ OPTIMAL, UNBOUNDED, INFEASIBLE, AUX_UNBOUNDED, NO_DEGENERATE_PIVOT, BAD_ARGUMENT
     DEVICE_ERROR, DIVIDE_BY_ZERO, PIVOT_LIMIT = range(10)
 CAND_HEADER = 8
 BATCH_LDS_BYTES = 163840   # LPX_BATCH_LDS_BYTES
+ROUTES = ("cold", "primal", "dual")   # LPX_ROUTE_*
 PRICING = {"reference": 0, "first-positive": 0, "dantzig": 1, 0: 0, 1: 1}
 
 # lpx_option (include/lpx.h)
@@ -173,6 +174,12 @@ SYMBOLS = [
                                       C.POINTER(SolveResult), dp, ip]),
     ("lpx_solve_scenarios", C.c_int, [C.c_int32, C.c_int32, dp, C.c_int64, C.c_int32, dp, C.c_int64, dp, C.c_int64, ip,
                                       C.POINTER(SolveOptions), C.POINTER(SolveResult), dp, ip]),
+    ("lpx_scenarios_set_basis", C.c_int, [C.c_void_p, ip, ip]),
+    ("lpx_scenarios_resolve", C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, dp, C.c_int64, ip, C.c_int64, ip, C.c_int32,
+                                        C.POINTER(SolveResult), dp, ip, ip]),
+    ("lpx_solve_scenarios_from_basis", C.c_int, [C.c_int32, C.c_int32, dp, C.c_int64, ip, C.c_int32, dp, C.c_int64, dp,
+                                                 C.c_int64, ip, C.POINTER(SolveOptions), C.POINTER(SolveResult), dp, ip,
+                                                 ip]),
 ]
 
 _lib = None

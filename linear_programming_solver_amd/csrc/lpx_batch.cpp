@@ -1,6 +1,7 @@
 // Batched solve behind the C ABI (include/lpx.h): many small LPs in ONE launch, one workgroup per LP with the LP's whole
 // state in LDS (lpx_batch.inc: k_batch_simplex runs the loop, k_batch_solve the whole of LPSolver.solve with phase 1,
-// k_batch_scenarios the same for many (b, c) on one matrix: lpx_scenarios at the end of this file).
+// k_batch_scenarios the same for many (b, c) on one matrix, k_scenarios_crash and k_batch_resolve the re-solve of such
+// scenarios from a shared basis: lpx_scenarios at the end of this file).
 // The handle keeps one HBM image per LP (lpxk::BatchLayout).  lpx_solve_batch and lpx_solve_batch_all are built from one
 // set of pieces (Forms, check_one_shot, Gathered, solve_alone, stamp_seconds).  Every argument is checked before the first
 // device call, so a bad call answers LPX_BAD_ARGUMENT on a machine without a GPU too.
@@ -743,11 +744,19 @@ struct lpx_scenarios {
   double *d_b = nullptr, *d_c = nullptr, *d_sv = nullptr, *d_x = nullptr;
   int32_t *d_flags = nullptr, *d_order = nullptr, *d_si32 = nullptr, *d_perm = nullptr;
   int64_t* d_si64 = nullptr;
+  // re-solve from a shared basis (lpx_scenarios_set_basis): the eta file of the crash, the matrix and the permutation at
+  // the basis; per scenario the route k_batch_resolve took
+  bool has_basis = false;
+  int32_t n_eta = 0;
+  double *d_eta = nullptr, *d_A_basis = nullptr;
+  int32_t *d_perm_basis = nullptr, *d_wanted = nullptr, *d_info = nullptr, *d_route = nullptr;
 };
 
 namespace {
 
 void free_scenario_buffers(lpx_scenarios* S) {
+  (void)hipFree(S->d_route);
+  S->d_route = nullptr;
   (void)hipFree(S->d_b);
   (void)hipFree(S->d_c);
   (void)hipFree(S->d_sv);
@@ -769,6 +778,11 @@ void free_scenarios(lpx_scenarios* S) {
     free_scenario_buffers(S);
     (void)hipFree(S->d_A);
     (void)hipFree(S->d_order);
+    (void)hipFree(S->d_eta);
+    (void)hipFree(S->d_A_basis);
+    (void)hipFree(S->d_perm_basis);
+    (void)hipFree(S->d_wanted);
+    (void)hipFree(S->d_info);
     if (S->stream) (void)hipStreamDestroy(S->stream);
   }
   delete S;
@@ -859,6 +873,7 @@ int scenarios_reserve(lpx_scenarios* S, int32_t count) {
   HIP_TRY(hipMalloc((void**)&S->d_si32, 4 * cnt * sizeof(int32_t)));
   HIP_TRY(hipMalloc((void**)&S->d_perm, std::max<size_t>(cnt * (n + m), 1) * sizeof(int32_t)));
   HIP_TRY(hipMalloc((void**)&S->d_si64, 2 * cnt * sizeof(int64_t)));
+  HIP_TRY(hipMalloc((void**)&S->d_route, cnt * sizeof(int32_t)));
   S->cap = count;
   return 0;
 }
@@ -973,6 +988,200 @@ int scenarios_solve_checked(const char* who, lpx_scenarios* S, int32_t count, co
   return 0;
 }
 
+// ---- re-solve from a shared basis -----------------------------------------------------------------------------------------
+// m variable ids, each in [0, n + m), all distinct
+int check_basis(const char* who, int32_t m, int32_t n, const int32_t* basis) {
+  std::vector<char> seen((size_t)n + m, 0);
+  char msg[200];
+  for (int32_t i = 0; i < m; i++) {
+    const int32_t id = basis[i];
+    if (id < 0 || id >= n + m) {
+      snprintf(msg, sizeof msg, "%s: basis entry %d names variable id %d outside 0..%d", who, i, id, n + m - 1);
+      return fail(LPX_BAD_ARGUMENT, msg);
+    }
+    if (seen[id]) {
+      snprintf(msg, sizeof msg, "%s: basis entry %d repeats variable id %d", who, i, id);
+      return fail(LPX_BAD_ARGUMENT, msg);
+    }
+    seen[id] = 1;
+  }
+  return 0;
+}
+
+// the checked core of lpx_scenarios_set_basis: ONE workgroup of k_scenarios_crash brings the handle's matrix to the basis
+int scenarios_set_basis_checked(const char* who, lpx_scenarios* S, const int32_t* basis, int32_t* crash_pivots_out) {
+  S->has_basis = false;
+  S->n_eta = 0;
+  if (crash_pivots_out) *crash_pivots_out = 0;
+  if (!basis) return 0;
+  const int32_t m = S->m, n = S->n;
+  std::vector<int32_t> wanted((size_t)std::max(n + m, 1), 0);
+  for (int32_t i = 0; i < m; i++) wanted[basis[i]] = 1;
+  HIP_TRY(hipSetDevice(S->device));
+  if (!S->d_eta) {
+    const size_t etas = (size_t)std::min(m, n) * (size_t)lpxk::eta_stride(m, n);
+    HIP_TRY(hipMalloc((void**)&S->d_eta, std::max<size_t>(etas, 1) * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&S->d_A_basis, std::max<size_t>((size_t)m * n, 1) * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&S->d_perm_basis, wanted.size() * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void**)&S->d_wanted, wanted.size() * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void**)&S->d_info, 2 * sizeof(int32_t)));
+  }
+  HIP_TRY(hipMemcpyAsync(S->d_wanted, wanted.data(), wanted.size() * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
+  lpxk::ScenarioCrashArgs a{};
+  a.count = 1;
+  a.m = m;
+  a.n = n;
+  a.A = S->d_A;
+  a.wanted = S->d_wanted;
+  a.A_out = S->d_A_basis;
+  a.perm_out = S->d_perm_basis;
+  a.eta = S->d_eta;
+  a.info = S->d_info;
+  a.fused = S->fused;
+  a.lds_bytes = (int32_t)std::max<int64_t>(lpxk::kBatchScratchBytes, lds_bytes_of(m, n));
+  a.threads = threads_or_env(threads_of(m, n));
+  HIP_TRY(lpxk::launch_scenarios_crash(a, S->stream));
+  int32_t info[2] = {0, -2};
+  HIP_TRY(hipMemcpyAsync(info, S->d_info, sizeof info, hipMemcpyDeviceToHost, S->stream));
+  HIP_TRY(hipStreamSynchronize(S->stream));
+  if (info[1] == -2) return fail(LPX_DEVICE_ERROR, std::string(who) + ": the kernel and the host disagree about the layout");
+  if (info[1] >= 0) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: basis is singular at variable id %d", who, info[1]);
+    return fail(LPX_BAD_ARGUMENT, msg);
+  }
+  S->n_eta = info[0];
+  S->has_basis = true;
+  if (crash_pivots_out) *crash_pivots_out = info[0];
+  return 0;
+}
+
+// the checked core of lpx_scenarios_resolve: flags from check_scenario_solve, count > 0, the handle has a basis
+int scenarios_resolve_checked(const char* who, lpx_scenarios* S, int32_t count, const double* b, int64_t ldb, const double* c,
+                              int64_t ldc, const std::vector<int32_t>& flags, int64_t max_pivots, const int32_t* restore_order,
+                              int32_t restore_order_len, lpx_solve_result* results, double* x_out, int32_t* perm_out,
+                              int32_t* route_out) {
+  const double t_start = now_s();
+  const int32_t m = S->m, n = S->n;
+  init_results(results, count);
+  HIP_TRY(hipSetDevice(S->device));
+  if (int rc = scenarios_reserve(S, count)) return rc;
+  const size_t cnt = (size_t)count;
+  if (int rc = upload_vectors(S, S->d_b, b, ldb, m, count)) return rc;
+  if (int rc = upload_vectors(S, S->d_c, c, ldc, n, count)) return rc;
+  HIP_TRY(hipMemcpyAsync(S->d_flags, flags.data(), cnt * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
+  lpxk::BatchResolveArgs a{};
+  a.count = count;
+  a.m = m;
+  a.n = n;
+  a.A = S->d_A_basis;
+  a.b = S->d_b;
+  a.c = S->d_c;
+  a.ldb = ldb == 0 ? 0 : m;
+  a.ldc = ldc == 0 ? 0 : n;
+  a.flags = S->d_flags;
+  a.status = S->d_si32;
+  a.phase1_used = a.status + cnt;
+  a.x0_slot = a.status + 2 * cnt;
+  a.n_final = a.status + 3 * cnt;
+  a.pivots1 = S->d_si64;
+  a.pivots2 = a.pivots1 + cnt;
+  a.v = S->d_sv;
+  a.x_out = x_out ? S->d_x : nullptr;
+  a.perm_out = perm_out ? S->d_perm : nullptr;
+  a.max_pivots = max_pivots < 0 ? -1 : max_pivots;
+  a.dantzig = S->pricing == 1;
+  a.fused = S->fused;
+  a.lds_bytes = (int32_t)std::max<int64_t>(lpxk::kBatchScratchBytes, lds_bytes_of(m, n));
+  a.threads = threads_or_env(threads_of(m, n));
+  a.perm0 = S->d_perm_basis;
+  a.eta = S->d_eta;
+  a.n_eta = S->n_eta;
+  a.route = S->d_route;
+  std::vector<int32_t> h_route(cnt), h_i32(4 * cnt);
+  std::vector<int64_t> h_i64(2 * cnt);
+  std::vector<double> h_v(cnt);
+  HIP_TRY(hipStreamSynchronize(S->stream));   // the uploads are through: seconds_pivots is the launches alone
+  const double t0 = now_s();
+  HIP_TRY(lpxk::launch_batch_resolve(a, S->stream));
+  HIP_TRY(hipStreamSynchronize(S->stream));
+  double t_pivots = now_s() - t0;
+  HIP_TRY(hipMemcpyAsync(h_route.data(), S->d_route, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+  HIP_TRY(hipMemcpyAsync(h_i32.data(), S->d_si32, h_i32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+  HIP_TRY(hipMemcpyAsync(h_i64.data(), S->d_si64, h_i64.size() * sizeof(int64_t), hipMemcpyDeviceToHost, S->stream));
+  HIP_TRY(hipMemcpyAsync(h_v.data(), S->d_sv, h_v.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+  HIP_TRY(hipStreamSynchronize(S->stream));
+  std::vector<int32_t> cold;
+  bool device_error = false;
+  for (int32_t k = 0; k < count; k++) {
+    if (h_route[k] == LPX_ROUTE_COLD) {
+      cold.push_back(k);
+      continue;
+    }
+    lpx_solve_result& r = results[k];
+    r.status = h_i32[k];
+    r.phase1_used = 0;
+    r.x0_slot = -1;
+    r.pivots_phase1 = h_i64[k];
+    r.pivots_phase2 = h_i64[cnt + k];
+    fill_objective(r, h_v[k], (flags[k] & 1) != 0);
+    device_error |= r.status == LPX_DEVICE_ERROR;
+  }
+  if (device_error) {
+    stamp_seconds(results, count, t_start, t_pivots);
+    return fail(LPX_DEVICE_ERROR, std::string(who) + ": the kernel and the host disagree about a scenario's layout");
+  }
+  // x and perm of the warm scenarios (their final state is always m x n): all of them, one copy each into the caller's
+  // arrays; else through a host copy, row by row -- the cold solve below reuses the device rows
+  const size_t xw = (size_t)n, pw = (size_t)n + m;
+  if (cold.empty()) {
+    if (x_out && xw > 0) HIP_TRY(hipMemcpyAsync(x_out, S->d_x, cnt * xw * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    if (perm_out && pw > 0) HIP_TRY(hipMemcpyAsync(perm_out, S->d_perm, cnt * pw * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+    HIP_TRY(hipStreamSynchronize(S->stream));
+  } else {
+    std::vector<double> hx(x_out ? cnt * xw : 0);
+    std::vector<int32_t> hp(perm_out ? cnt * pw : 0);
+    if (!hx.empty()) HIP_TRY(hipMemcpyAsync(hx.data(), S->d_x, hx.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+    if (!hp.empty()) HIP_TRY(hipMemcpyAsync(hp.data(), S->d_perm, hp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+    HIP_TRY(hipStreamSynchronize(S->stream));
+    for (int32_t k = 0; k < count; k++) {
+      if (h_route[k] == LPX_ROUTE_COLD) continue;
+      if (!hx.empty()) memcpy(x_out + k * xw, hx.data() + k * xw, xw * sizeof(double));
+      if (!hp.empty()) memcpy(perm_out + k * pw, hp.data() + k * pw, pw * sizeof(int32_t));
+    }
+    // the cold scenarios: lpx_scenarios_solve on their rows of b and c, gathered; results, x and perm scattered back
+    const int32_t nc = (int32_t)cold.size();
+    std::vector<double> gb(ldb == 0 ? 0 : (size_t)nc * m), gc(ldc == 0 ? 0 : (size_t)nc * n);
+    std::vector<int32_t> gflags(nc);
+    bool any_p1 = false;
+    for (int32_t t = 0; t < nc; t++) {
+      const int32_t k = cold[t];
+      if (ldb != 0 && m > 0) memcpy(&gb[(size_t)t * m], b + k * ldb, (size_t)m * sizeof(double));
+      if (ldc != 0 && n > 0) memcpy(&gc[(size_t)t * n], c + k * ldc, (size_t)n * sizeof(double));
+      gflags[t] = flags[k];
+      any_p1 |= (flags[k] & 2) != 0;
+    }
+    std::vector<lpx_solve_result> res(nc);
+    std::vector<double> tx(x_out ? (size_t)nc * xw : 0);
+    std::vector<int32_t> tp((size_t)nc * pw, -1);   // a row the solve leaves alone (ended inside phase 1) still starts with -1
+    if (int rc = scenarios_solve_checked(who, S, nc, ldb == 0 ? b : gb.data(), ldb == 0 ? 0 : m, ldc == 0 ? c : gc.data(),
+                                         ldc == 0 ? 0 : n, gflags, any_p1, max_pivots, restore_order, restore_order_len,
+                                         res.data(), tx.empty() ? nullptr : tx.data(), tp.empty() ? nullptr : tp.data()))
+      return rc;
+    t_pivots += res[0].seconds_pivots;
+    for (int32_t t = 0; t < nc; t++) {
+      const int32_t k = cold[t];
+      results[k] = res[t];
+      if (pw > 0 && tp[(size_t)t * pw] < 0) continue;
+      if (!tx.empty()) memcpy(x_out + k * xw, tx.data() + t * xw, xw * sizeof(double));
+      if (perm_out && pw > 0) memcpy(perm_out + k * pw, tp.data() + t * pw, pw * sizeof(int32_t));
+    }
+  }
+  if (route_out) memcpy(route_out, h_route.data(), cnt * sizeof(int32_t));
+  stamp_seconds(results, count, t_start, t_pivots);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int lpx_scenarios_create(int32_t m, int32_t n, const double* A, int64_t lda, int device, lpx_scenarios** out) {
@@ -992,6 +1201,7 @@ extern "C" int lpx_scenarios_set_option(lpx_scenarios* S, int32_t key, int64_t v
   if (!S) return fail(LPX_BAD_ARGUMENT, "lpx_scenarios_set_option: NULL handle");
   if (key != LPX_OPT_FUSED || value < 0 || value > 2)
     return fail(LPX_BAD_ARGUMENT, "lpx_scenarios_set_option: only LPX_OPT_FUSED (0, 1, 2) applies to a scenario batch");
+  if (S->fused != (value == 1)) S->has_basis = false;   // the matrix at the basis carries the roundings of the mode it was made in
   S->fused = value == 1;   // 2 = by size: a shape that fits a workgroup is far below the switch, i.e. 0
   return 0;
 }
@@ -1048,6 +1258,88 @@ extern "C" int lpx_solve_scenarios(int32_t m, int32_t n, const double* A, int64_
                                        o.restore_order_len, results, x_out, perm_out))
     return rc;
   stamp_seconds(results, count, t_start, results[0].seconds_pivots);   // the times of the whole call, creation included
+  return 0;
+}
+
+// The basis every later lpx_scenarios_resolve starts from: m variable ids (perm's numbering), NULL clears it
+extern "C" int lpx_scenarios_set_basis(lpx_scenarios* S, const int32_t* basis, int32_t* crash_pivots_out) {
+  const char* who = "lpx_scenarios_set_basis";
+  if (crash_pivots_out) *crash_pivots_out = 0;
+  if (!S) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL handle");
+  if (basis)
+    if (int rc = check_basis(who, S->m, S->n, basis)) return rc;
+  DeviceRestore keep_device;
+  return scenarios_set_basis_checked(who, S, basis, crash_pivots_out);
+}
+
+// lpx_scenarios_solve from the handle's basis: ONE launch of k_batch_resolve, then the scenarios it routed cold through
+// the launch lpx_scenarios_solve makes
+extern "C" int lpx_scenarios_resolve(lpx_scenarios* S, int32_t count, const double* b, int64_t ldb, const double* c, int64_t ldc,
+                                     const int32_t* maximize, int64_t max_pivots, const int32_t* restore_order,
+                                     int32_t restore_order_len, lpx_solve_result* results, double* x_out, int32_t* perm_out,
+                                     int32_t* route_out) {
+  const char* who = "lpx_scenarios_resolve";
+  if (!S) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL handle");
+  std::vector<int32_t> flags;
+  bool any_p1 = false;
+  if (int rc = check_scenario_solve(who, S->m, S->n, count, b, ldb, c, ldc, maximize, restore_order, restore_order_len, results,
+                                    flags, &any_p1))
+    return rc;
+  if (!S->has_basis) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": the handle has no basis (lpx_scenarios_set_basis)");
+  if (count == 0) return 0;
+  DeviceRestore keep_device;
+  return scenarios_resolve_checked(who, S, count, b, ldb, c, ldc, flags, max_pivots, restore_order, restore_order_len, results,
+                                   x_out, perm_out, route_out);
+}
+
+// create, set_basis, resolve, destroy
+extern "C" int lpx_solve_scenarios_from_basis(int32_t m, int32_t n, const double* A, int64_t lda, const int32_t* basis,
+                                              int32_t count, const double* b, int64_t ldb, const double* c, int64_t ldc,
+                                              const int32_t* maximize, const lpx_solve_options* opts, lpx_solve_result* results,
+                                              double* x_out, int32_t* perm_out, int32_t* route_out) {
+  const char* who = "lpx_solve_scenarios_from_basis";
+  lpx_solve_options o{};
+  o.max_pivots = -1;
+  if (opts) o = *opts;
+  if (o.keep_state || o.perm_out || o.x_out)
+    return fail(LPX_BAD_ARGUMENT, std::string(who) + ": opts->keep_state, opts->perm_out and opts->x_out must be NULL");
+  if (o.pricing != 0 && o.pricing != 1) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": bad pricing");
+  if (int rc = check_scenario_matrix(who, m, n, A, lda, o.device)) return rc;
+  if (!basis) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": basis is NULL");
+  if (int rc = check_basis(who, m, n, basis)) return rc;
+  std::vector<int32_t> flags;
+  bool any_p1 = false;
+  if (int rc = check_scenario_solve(who, m, n, count, b, ldb, c, ldc, maximize, o.restore_order, o.restore_order_len, results,
+                                    flags, &any_p1))
+    return rc;
+  if (count == 0) return 0;
+  const double t_start = now_s();
+  DeviceRestore keep_device;
+  ScenariosGuard guard;
+  if (int rc = scenarios_create_checked(m, n, A, lda, o.device, &guard.S)) return rc;
+  guard.S->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
+  guard.S->pricing = o.pricing;
+  if (int rc = scenarios_set_basis_checked(who, guard.S, basis, nullptr)) return rc;
+  if (int rc = scenarios_resolve_checked(who, guard.S, count, b, ldb, c, ldc, flags, o.max_pivots, o.restore_order,
+                                         o.restore_order_len, results, x_out, perm_out, route_out))
+    return rc;
+  stamp_seconds(results, count, t_start, results[0].seconds_pivots);   // the times of the whole call, creation and crash included
+  return 0;
+}
+
+// What the launch of lpx_scenarios_resolve looks like for this handle, and the entries of its eta file
+// (scripts/bench_scenarios_resolve.py): not part of include/lpx.h
+extern "C" int lpxi_scenarios_resolve_launch_info(lpx_scenarios* S, int32_t* threads, int32_t* lds_bytes, int32_t* blocks_per_cu,
+                                                  int32_t* etas) {
+  if (!S) return fail(LPX_BAD_ARGUMENT, "lpxi_scenarios_resolve_launch_info: NULL handle");
+  DeviceRestore keep_device;
+  HIP_TRY(hipSetDevice(S->device));
+  const int t = threads_or_env(threads_of(S->m, S->n));
+  const int lds = (int)std::min<int64_t>(std::max<int64_t>(lpxk::kBatchScratchBytes, lds_bytes_of(S->m, S->n)), INT32_MAX);
+  if (threads) *threads = t;
+  if (lds_bytes) *lds_bytes = lds;
+  if (blocks_per_cu) *blocks_per_cu = lpxk::batch_resolve_blocks_per_cu(t, lds);
+  if (etas) *etas = S->has_basis ? S->n_eta : -1;
   return 0;
 }
 

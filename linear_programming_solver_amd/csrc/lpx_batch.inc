@@ -524,7 +524,215 @@ __global__ __launch_bounds__(kThreads) void k_batch_scenarios(const BatchScenari
   batch_solve_body(batch_lds, BatchScenarioEnds(a, k), a.m, a.n);
 }
 
-// Host side of the three kernels.  K names a kernel template and its argument block; the workgroup size picks the
+// ---- re-solve from a shared basis: k_scenarios_crash once per basis, k_batch_resolve per launch of scenarios ------------------
+// A scenario sweep is a base case plus perturbations, and the base case's optimal basis is optimal or nearly so for most of
+// them.  The crash brings the shared matrix to that basis once and records what its pivots did to b, c and v (the eta file,
+// lpx_kernels.h); a scenario replays that in O(m + n) per crash pivot, looks at its b' and c' and takes one of three routes:
+//   primal  b' >= 0: the loop above from (A', b', c')
+//   dual    some b' < 0 and no c'[j] > 1e-9: batch_dual_loop below until b' >= -1e-9, then the loop above (which normally
+//           ends at once).  No auxiliary LP, no restore: phase 1 is never entered
+//   cold    neither: the workgroup writes the route and ends; the host solves the scenario from the slack basis
+// Every pivot is batch_pivot, so the bits are those of the reference's pivot in either arithmetic mode.
+
+// k_scenarios_crash: ONE workgroup, the matrix in LDS at the odd pitch with b = c = 0, v = 0 and the identity permutation.
+// One pass over the slots j = 0..n-1: where perm[j] is wanted, pivot on the largest |A[i][j]| among the rows whose basic
+// variable is not wanted (lowest row on ties, a NaN never; none, or a maximum <= 1e-9: the basis is singular at perm[j]).
+// One pass is enough: the pivot leaves an unwanted variable in slot j, and a wanted one never leaves the basis.
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void k_scenarios_crash(const ScenarioCrashArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double batch_lds[];
+  const int m = a.m, n = a.n, tid = threadIdx.x, T = blockDim.x;
+  const BatchLayout L = batch_layout(m, n);
+  if (blockIdx.x != 0) return;
+  if (L.lds_bytes > a.lds_bytes) {  // the host sized the launch from the same formula: never taken, and never out of bounds
+    if (tid == 0) { a.info[0] = 0; a.info[1] = -2; }
+    return;
+  }
+  const BatchLp S = batch_lp(batch_lds, L, m, n, tid, T, 0);
+  const int ld = S.ld;
+  for (int i = S.wave; i < m; i += S.nw)
+    for (int j = S.lane; j < n; j += 64) S.A[i * ld + j] = a.A[(int64_t)i * n + j];
+  for (int i = tid; i < m; i += T) S.b[i] = 0.0;
+  for (int j = tid; j < n; j += T) S.c[j] = 0.0;
+  if (tid == 0) *S.vp = 0.0;
+  for (int s = tid; s < n + m; s += T) S.perm[s] = s;
+  __syncthreads();
+  const int64_t stride = eta_stride(m, n);
+  int t = 0, singular = -1;
+  for (int j = 0; j < n; ++j) {
+    const int32_t id = S.perm[j];
+    if (!a.wanted[id]) continue;
+    RatioRow best = rr_none();                          // (-|A[i][j]|, i): the lexicographic minimum is the largest, lowest row
+    for (int i = tid; i < m; i += T) {
+      const double x = fabs(S.A[i * ld + j]);
+      if (x > kEps && !a.wanted[S.perm[n + i]]) best = rr_min(best, RatioRow{-x, i, 0});
+    }
+    best = batch_reduce(best, S.sh_l, S.lane, S.wave, S.nw);
+    if (best.row == INT_MAX) { singular = id; break; }
+    const int l = best.row;
+    batch_save_column(S, j);
+    batch_pivot(S, j, l);
+    double* const E = a.eta + t * stride;               // col[] is as saved, row l is the normalised pivot row
+    if (tid == 0) { E[0] = (double)j; E[1] = (double)l; E[2] = S.col[l]; E[3] = 0.0; }
+    for (int i = tid; i < m; i += T) E[4 + i] = S.col[i];
+    for (int q = tid; q < n; q += T) E[4 + m + q] = S.A[l * ld + q];
+    ++t;                                                // the next write of col[] stands behind the barrier of batch_reduce
+  }
+  if (tid == 0) { a.info[0] = t; a.info[1] = singular; }
+  if (singular >= 0) return;
+  for (int i = S.wave; i < m; i += S.nw)
+    for (int j = S.lane; j < n; j += 64) a.A_out[(int64_t)i * n + j] = S.A[i * ld + j];
+  for (int s = tid; s < n + m; s += T) a.perm_out[s] = S.perm[s];
+}
+
+// What batch_pivot does to b, c and v for every entry of the eta file, in order, on the b and c in LDS; returns v.  One
+// barrier per entry: c[e] and b[l] are read by every thread in front of it and written behind it by the threads that own
+// them in the strided loops (every thread carries the two new values in registers, should the next entry read them).
+// The next entry's header and each thread's first element of its column and row are loaded before the barrier, so their
+// latency hides behind the entry at hand.  Ends behind a barrier.
+__device__ __forceinline__ double batch_replay(const BatchLp& S, const double* __restrict__ eta, int n_eta) {
+  const int m = S.m, n = S.n, tid = S.tid, T = S.T;
+  const int64_t stride = eta_stride(m, n);
+  const double* E = eta;
+  double h0 = 0.0, h1 = 0.0, h2 = 1.0, hc = 0.0, hp = 0.0;
+  if (n_eta > 0) {
+    h0 = E[0]; h1 = E[1]; h2 = E[2];
+    if (tid < m) hc = E[4 + tid];
+    if (tid < n) hp = E[4 + m + tid];
+  }
+  double v = 0.0, ce_new = 0.0, bl_new = 0.0;
+  int pe = -1, pl = -1;
+  for (int t = 0; t < n_eta; ++t) {
+    const int e = (int)h0, l = (int)h1;
+    const double piv = h2, col0 = hc, prow0 = hp;
+    const double* const col = E + 4;
+    const double* const prow = col + m;
+    E += stride;
+    if (t + 1 < n_eta) {
+      h0 = E[0]; h1 = E[1]; h2 = E[2];
+      if (tid < m) hc = E[4 + tid];
+      if (tid < n) hp = E[4 + m + tid];
+    }
+    const double pc = e == pe ? ce_new : S.c[e];
+    const double bl = __ddiv_rn(l == pl ? bl_new : S.b[l], piv);                    // :146
+    if (tid < n && tid != e) S.c[tid] = submul(S.c[tid], pc, prow0);                // :177
+    for (int j = tid + T; j < n; j += T)
+      if (j != e) S.c[j] = submul(S.c[j], pc, prow[j]);
+    if (tid < m && tid != l) S.b[tid] = submul(S.b[tid], col0, bl);                 // :164
+    for (int i = tid + T; i < m; i += T)
+      if (i != l) S.b[i] = submul(S.b[i], col[i], bl);
+    v = addmul(v, bl, pc);                                                          // :171
+    ce_new = -__ddiv_rn(pc, piv);                                                   // :172
+    bl_new = bl;
+    pe = e;
+    pl = l;
+    __syncthreads();
+    if (tid == e % T) S.c[e] = ce_new;
+    if (tid == l % T) S.b[l] = bl_new;
+  }
+  __syncthreads();
+  return v;
+}
+
+// minInB (LPSolver.java:375-386) on the b in LDS: from 1e50, lowest row on ties, a NaN never; one barrier
+__device__ __forceinline__ RatioRow batch_min_in_b(const BatchLp& S) {
+  RatioRow mb = rr_none();
+  for (int i = S.tid; i < S.m; i += S.T) {
+    const double bi = S.b[i];
+    if (bi < kInf) mb = rr_min(mb, RatioRow{bi, i, 0});
+  }
+  return batch_reduce(mb, S.sh_l, S.lane, S.wave, S.nw);
+}
+
+// The dual simplex loop from a state with no c[j] > 1e-9 and some b[i] < 0.  One iteration: the leaving row l by minInB on
+// the current b (not below -1e-9: done, 0); the entering slot e with the smallest c[j] / A[l][j] among A[l][j] < -1e-9, a
+// strict < scan from 1e50, lowest slot on ties (none: LPX_INFEASIBLE -- row l says a sum of nonnegative terms is
+// negative); the budget, where batch_loop has it (LPX_PIVOT_LIMIT); the pivot.  Row l is contiguous in LDS, so the
+// ratio scan is conflict-free.  Five barriers per iteration.
+__device__ __forceinline__ int batch_dual_loop(const BatchLp& S, int64_t max_pivots, int64_t& pivots) {
+  for (;;) {
+    const RatioRow mb = batch_min_in_b(S);
+    if (mb.row == INT_MAX || !(mb.ratio < -kEps)) return 0;
+    const int l = mb.row;
+    const double* const row = S.A + l * S.ld;
+    RatioRow best = rr_none();
+    for (int j = S.tid; j < S.n; j += S.T) {
+      const double alj = row[j];
+      if (alj < -kEps) {
+        const double r = __ddiv_rn(S.c[j], alj);
+        if (r < kInf) best = rr_min(best, RatioRow{r, j, 0});
+      }
+    }
+    best = batch_reduce(best, S.sh_e, S.lane, S.wave, S.nw);
+    if (best.row == INT_MAX) return 2 /* LPX_INFEASIBLE */;
+    if (max_pivots >= 0 && pivots >= max_pivots) return 9 /* LPX_PIVOT_LIMIT */;
+    batch_save_column(S, best.row);
+    batch_pivot(S, best.row, l);
+    pivots++;
+  }
+}
+
+// k_batch_resolve: one workgroup per scenario, LDS of batch_layout(m, n) -- no auxiliary layout is ever needed.
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void k_batch_resolve(const BatchResolveArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double batch_lds[];
+  const int k = blockIdx.x;
+  if (k >= a.count) return;
+  const int m = a.m, n = a.n, tid = threadIdx.x, T = blockDim.x;
+  const BatchLayout L = batch_layout(m, n);
+  if (L.lds_bytes > a.lds_bytes) {  // the host sized the launch from the same formula: never taken, and never out of bounds
+    if (tid == 0) {
+      a.route[k] = 1;
+      a.status[k] = 7 /* LPX_DEVICE_ERROR */;
+      a.phase1_used[k] = 0; a.x0_slot[k] = -1; a.n_final[k] = n; a.pivots1[k] = 0; a.pivots2[k] = 0; a.v[k] = 0.0;
+    }
+    return;
+  }
+  const BatchScenarioEnds io(a, k);
+  const BatchLp S = batch_lp(batch_lds, L, m, n, tid, T, a.dantzig);
+  const bool maximize = io.maximize();
+  for (int i = tid; i < m; i += T) S.b[i] = io.gb[i];
+  for (int j = tid; j < n; j += T) S.c[j] = maximize ? io.gc[j] : -io.gc[j];       // :86-89
+  __syncthreads();
+  const double v0 = batch_replay(S, a.eta, a.n_eta);
+  const RatioRow mb = batch_min_in_b(S);
+  const bool needs_dual = mb.row != INT_MAX && mb.ratio < 0.0;                      // LPSolver.java:119 at the basis
+  RatioRow ent = batch_entering(S);
+  if (needs_dual && ent.row != INT_MAX) {
+    if (tid == 0) a.route[k] = 0 /* LPX_ROUTE_COLD */;
+    return;
+  }
+  const int ld = S.ld;
+  for (int i = S.wave; i < m; i += S.nw)
+    for (int j = S.lane; j < n; j += 64) S.A[i * ld + j] = a.A[(int64_t)i * n + j];
+  for (int s = tid; s < n + m; s += T) S.perm[s] = a.perm0[s];
+  if (tid == 0) *S.vp = v0;
+  __syncthreads();
+  int status = 0, none = -1;
+  int64_t pivots1 = 0, pivots2 = 0;
+  if (needs_dual) {
+    status = batch_dual_loop(S, a.max_pivots, pivots1);
+    if (status == 0) ent = batch_entering(S);
+  }
+  if (status == 0) {
+    const int64_t lim2 = a.max_pivots < 0 ? -1 : (a.max_pivots > pivots1 ? a.max_pivots - pivots1 : 0);
+    status = batch_loop(S, ent, lim2, pivots2, none);
+  }
+  __syncthreads();
+  io.store(S);
+  if (tid == 0) {
+    a.route[k] = needs_dual ? 2 /* LPX_ROUTE_DUAL */ : 1 /* LPX_ROUTE_PRIMAL */;
+    a.status[k] = status;
+    a.phase1_used[k] = 0;
+    a.x0_slot[k] = -1;
+    a.n_final[k] = n;
+    a.pivots1[k] = pivots1;
+    a.pivots2[k] = pivots2;
+    a.v[k] = *S.vp;
+  }
+}
+
+// Host side of the kernels.  K names a kernel template and its argument block; the workgroup size picks the
 // instantiation (64, 256, 1024) here and nowhere else.
 struct BatchSimplexKernel {
   using Args = BatchArgs;
@@ -537,6 +745,15 @@ struct BatchSolveKernel {
 struct BatchScenarioKernel {
   using Args = BatchScenarioArgs;
   template <int kThreads> static const void* fn() { return (const void*)k_batch_scenarios<kThreads>; }
+};
+
+struct ScenarioCrashKernel {
+  using Args = ScenarioCrashArgs;
+  template <int kThreads> static const void* fn() { return (const void*)k_scenarios_crash<kThreads>; }
+};
+struct BatchResolveKernel {
+  using Args = BatchResolveArgs;
+  template <int kThreads> static const void* fn() { return (const void*)k_batch_resolve<kThreads>; }
 };
 
 template <typename K>
@@ -572,3 +789,6 @@ hipError_t launch_batch_solve(const BatchSolveArgs& a, hipStream_t s) { return b
 int batch_solve_blocks_per_cu(int threads, int lds_bytes) { return batch_occupancy<BatchSolveKernel>(threads, lds_bytes); }
 hipError_t launch_batch_scenarios(const BatchScenarioArgs& a, hipStream_t s) { return batch_launch<BatchScenarioKernel>(a, s); }
 int batch_scenarios_blocks_per_cu(int threads, int lds_bytes) { return batch_occupancy<BatchScenarioKernel>(threads, lds_bytes); }
+hipError_t launch_scenarios_crash(const ScenarioCrashArgs& a, hipStream_t s) { return batch_launch<ScenarioCrashKernel>(a, s); }
+hipError_t launch_batch_resolve(const BatchResolveArgs& a, hipStream_t s) { return batch_launch<BatchResolveKernel>(a, s); }
+int batch_resolve_blocks_per_cu(int threads, int lds_bytes) { return batch_occupancy<BatchResolveKernel>(threads, lds_bytes); }

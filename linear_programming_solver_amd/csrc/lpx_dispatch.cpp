@@ -100,6 +100,15 @@ hipError_t launch_batch_scenarios(const BatchScenarioArgs& a, hipStream_t s) {
 int batch_scenarios_blocks_per_cu(int threads, int lds_bytes) {
   return std::min(plain::batch_scenarios_blocks_per_cu(threads, lds_bytes), fused::batch_scenarios_blocks_per_cu(threads, lds_bytes));
 }
+hipError_t launch_scenarios_crash(const ScenarioCrashArgs& a, hipStream_t s) {
+  return a.fused ? fused::launch_scenarios_crash(a, s) : plain::launch_scenarios_crash(a, s);
+}
+hipError_t launch_batch_resolve(const BatchResolveArgs& a, hipStream_t s) {
+  return a.fused ? fused::launch_batch_resolve(a, s) : plain::launch_batch_resolve(a, s);
+}
+int batch_resolve_blocks_per_cu(int threads, int lds_bytes) {
+  return std::min(plain::batch_resolve_blocks_per_cu(threads, lds_bytes), fused::batch_resolve_blocks_per_cu(threads, lds_bytes));
+}
 void launch_transpose(const double* dA, int64_t lda, double* dAt, int64_t ldat, int m, int n, hipStream_t s) {
   plain::launch_transpose(dA, lda, dAt, ldat, m, n, s);
 }

@@ -230,6 +230,34 @@ struct BatchScenarioArgs {
   int32_t lds_bytes;
   int32_t threads;
 };
+// Re-solve from a shared basis (k_scenarios_crash, k_batch_resolve).  The crash kernel brings the handle's matrix to the
+// basis ONCE and leaves an "eta file": per crash pivot t one entry of eta_stride(m, n) doubles
+//   [0] entering slot e_t   [1] leaving row l_t   [2] pivot element piv_t   [3] 0
+//   [4, 4 + m)          the entering column as batch_save_column saved it
+//   [4 + m, 4 + m + n)  row l_t after the pivot (the normalised pivot row, entry e_t = 1/piv_t)
+// which is all batch_pivot reads when it updates b, c and v: a scenario replays it in O(m + n) per entry.
+__host__ __device__ inline int64_t eta_stride(int64_t m, int64_t n) { return m + n + 4; }
+struct ScenarioCrashArgs {
+  int32_t count;             // 1: one workgroup
+  int32_t m, n;
+  const double* A;           // m x n, row-major at pitch n
+  const int32_t* wanted;     // [n + m] 1 where the variable id is to be basic
+  double* A_out;             // m x n at pitch n: the matrix at the basis
+  int32_t* perm_out;         // [n + m] the permutation at the basis
+  double* eta;               // room for min(m, n) entries
+  int32_t* info;             // [2] out: crash pivots made; the variable id at which the basis is singular, -1: none
+  int32_t fused;
+  int32_t lds_bytes;
+  int32_t threads;
+};
+// BatchScenarioArgs with A = the matrix at the basis; of flags only bit 0 is read, order and order_len not at all, and
+// the outputs of a scenario routed LPX_ROUTE_COLD (route[k] = 0) are left as they are.
+struct BatchResolveArgs : BatchScenarioArgs {
+  const int32_t* perm0;      // [n + m] the permutation at the basis
+  const double* eta;
+  int32_t n_eta;
+  int32_t* route;            // [count] out: LPX_ROUTE_*
+};
 
 // ---- launch wrappers --------------------------------------------------------------------------------------------
 // lpx_kernels.hip is compiled twice: plain (one rounding per reference operation) and fused (updates as one FMA).

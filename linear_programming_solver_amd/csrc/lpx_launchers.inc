@@ -79,4 +79,8 @@ int batch_solve_blocks_per_cu(int threads, int lds_bytes);
 // the same for a.count scenarios of one constraint matrix (k_batch_scenarios, lpx_batch.inc)
 hipError_t launch_batch_scenarios(const BatchScenarioArgs& a, hipStream_t s);
 int batch_scenarios_blocks_per_cu(int threads, int lds_bytes);
+// re-solve from a shared basis: the one-workgroup crash to the basis, and the scenarios from there (lpx_batch.inc)
+hipError_t launch_scenarios_crash(const ScenarioCrashArgs& a, hipStream_t s);
+hipError_t launch_batch_resolve(const BatchResolveArgs& a, hipStream_t s);
+int batch_resolve_blocks_per_cu(int threads, int lds_bytes);
 void launch_transpose(const double* dA, int64_t lda, double* dAt, int64_t ldat, int m, int n, hipStream_t s);

@@ -74,6 +74,36 @@ class LPScenarios:
         the ONE order of restoreInitialLP as original-variable indices (at most n; an empty one substitutes nothing).
         Returns a list of SolveInfo; .perm and .x are filled when the scenario's final state is m x n and None when its
         solve ended inside phase 1."""
+        return self._solve(False, b, c, maximize, max_pivots, restore_order)
+
+    def set_basis(self, ids):
+        """The basis every later resolve() starts from (lpx_scenarios_set_basis): the m variable ids that are to be basic,
+        in perm's numbering (0..n-1 the original variables, n..n+m-1 the slacks) -- the perm[n:] of a solved base case
+        will do -- or None to clear it.  Returns the pivots it took to bring the matrix there (0 for None).  A singular
+        basis raises and leaves the handle without one.  solve() never looks at the basis."""
+        m, n = self.m, self.n
+        arr = None
+        if ids is not None:
+            arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+            if arr.size != m:
+                raise ValueError("a basis has %d entries, got %d" % (m, arr.size))
+            if not arr.size:
+                arr = np.zeros(1, dtype=np.int32)   # m = 0: the empty basis, non-NULL
+        took = C.c_int32(0)
+        rc = self._L.lpx_scenarios_set_basis(self._h, None if arr is None else arr.ctypes.data_as(_lib.ip), C.byref(took))
+        if rc:
+            raise_for_status(rc)
+        return took.value
+
+    def resolve(self, b, c, maximize=None, max_pivots=-1, restore_order=None):
+        """solve() from the basis of set_basis (lpx_scenarios_resolve): every scenario's (b, c) is brought to the basis on
+        chip and then takes the primal loop (b' >= 0), a dual simplex loop followed by the primal one (some b' < 0, no
+        improving cost) or, where neither holds, exactly what solve() does.  Returns the SolveInfo list of solve(), each
+        entry with .route in {"cold", "primal", "dual"}; on the primal and dual routes pivots_phase1 counts the dual
+        loop, pivots_phase2 the primal loop, phase1_used is False and perm and x are always filled."""
+        return self._solve(True, b, c, maximize, max_pivots, restore_order)
+
+    def _solve(self, from_basis, b, c, maximize, max_pivots, restore_order):
         from .lp_solver import SolveInfo
         m, n = self.m, self.n
         cnt, b, ldb, c, ldc = scenario_arrays(m, n, b, c)
@@ -92,12 +122,19 @@ class LPScenarios:
         res = (_lib.SolveResult * max(cnt, 1))()
         x = np.full((cnt, n), -1.0)
         perm = np.full((cnt, n + m), -1, dtype=np.int32)   # -1 stays where the final state is not m x n
-        rc = self._L.lpx_scenarios_solve(self._h, cnt, b.ctypes.data_as(_lib.dp) if m else None, ldb,
-                                         c.ctypes.data_as(_lib.dp) if n else None, ldc,
-                                         None if mx is None else mx.ctypes.data_as(_lib.ip), int(max_pivots),
-                                         None if order is None else order.ctypes.data_as(_lib.ip), olen, res,
-                                         x.ctypes.data_as(_lib.dp) if x.size else None,
-                                         perm.ctypes.data_as(_lib.ip) if perm.size else None)
+        args = [self._h, cnt, b.ctypes.data_as(_lib.dp) if m else None, ldb, c.ctypes.data_as(_lib.dp) if n else None, ldc,
+                None if mx is None else mx.ctypes.data_as(_lib.ip), int(max_pivots),
+                None if order is None else order.ctypes.data_as(_lib.ip), olen, res,
+                x.ctypes.data_as(_lib.dp) if x.size else None, perm.ctypes.data_as(_lib.ip) if perm.size else None]
+        if from_basis:
+            route = np.zeros(max(cnt, 1), dtype=np.int32)
+            rc = self._L.lpx_scenarios_resolve(*args, route.ctypes.data_as(_lib.ip))
+        else:
+            rc = self._L.lpx_scenarios_solve(*args)
         if rc:
             raise_for_status(rc)
-        return [SolveInfo.of_batch_row(res[k], m, n, perm[k], x[k]) for k in range(cnt)]
+        infos = [SolveInfo.of_batch_row(res[k], m, n, perm[k], x[k]) for k in range(cnt)]
+        if from_basis:
+            for k, info in enumerate(infos):
+                info.route = _lib.ROUTES[route[k]]
+        return infos

@@ -28,6 +28,7 @@ class SolveInfo:
         self.seconds_pivots = res.seconds_pivots
         self.perm = perm
         self.x = x
+        self.route = None   # LPScenarios.resolve: "cold", "primal" or "dual"
 
     @classmethod
     def of_batch_row(cls, res, m, n, perm_row=None, x_row=None):
@@ -181,17 +182,22 @@ class LPSolver:
             self.last_batch_x = [info.x for info in infos]
         return answers
 
-    def solve_scenarios(self, A, b, c, maximize=None, restore_order=None):
+    def solve_scenarios(self, A, b, c, maximize=None, restore_order=None, basis=None):
         """LPSolver.solve for many scenarios of ONE constraint matrix (LPScenarios): b of
         shape (m,) or (count, m), c of shape (n,) or (count, n), maximize one flag per scenario (None: all maximise),
         restore_order the one order of restoreInitialLP (None: the default-name order).  Every scenario, phase 1 included,
         runs in ONE launch of the batch kernel.  Returns one entry per scenario exactly as solve_batch does: the Decimal
         solve() would return or the exception INSTANCE it would raise.  self.last_batch holds a SolveInfo per scenario,
-        self.last_batch_x the solutions (None where the final state is not m x n).  Single device only."""
+        self.last_batch_x the solutions (None where the final state is not m x n).  Single device only.
+        basis: the m variable ids of a basis to start every scenario from (LPScenarios.set_basis / resolve; the perm[n:]
+        of a solved base case); every SolveInfo then carries .route."""
         from .lp_scenarios import LPScenarios
         sc = LPScenarios(A, device=self.device, options=self._arith_options(), pricing=self.pricing)
         try:
-            infos = sc.solve(b, c, maximize=maximize, max_pivots=self.max_pivots, restore_order=restore_order)
+            if basis is not None:
+                sc.set_basis(basis)
+            run = sc.solve if basis is None else sc.resolve
+            infos = run(b, c, maximize=maximize, max_pivots=self.max_pivots, restore_order=restore_order)
         finally:
             sc.close()
         answers = []
