@@ -2,9 +2,11 @@
 // state in LDS (lpx_batch.inc: k_batch_simplex runs the loop, k_batch_solve the whole of LPSolver.solve with phase 1,
 // k_batch_scenarios the same for many (b, c) on one matrix, k_scenarios_crash and k_batch_resolve the re-solve of such
 // scenarios from a shared basis: lpx_scenarios at the end of this file).
-// The handle keeps one HBM image per LP (lpxk::BatchLayout).  lpx_solve_batch and lpx_solve_batch_all are built from one
-// set of pieces (Forms, check_one_shot, Gathered, solve_alone, stamp_seconds).  Every argument is checked before the first
-// device call, so a bad call answers LPX_BAD_ARGUMENT on a machine without a GPU too.
+// The handle keeps one HBM image per LP (lpxk::BatchLayout).  Every piece of the host path exists once: Forms,
+// check_one_shot, Gathered, solve_alone and stamp_seconds for the two batch one-shots; SolveScalars (the seven scalars a
+// kernel answers per LP) for the three solves; launch_scenarios, download_rows and with_scenarios for the scenario calls;
+// one LaunchShape for a launch and the lpxi_*_launch_info that describes it; DeviceBuf members own the device memory.
+// Every argument is checked before the first device call: a bad call answers LPX_BAD_ARGUMENT without a GPU too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -20,6 +23,97 @@
 namespace lpx_internal {
 void round6_text(double v, char* out, size_t cap);   // lpx_solver.cpp
 }
+
+namespace {
+
+double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// A device array that frees itself.  The device it was allocated on must be current when it goes: the destructors of the
+// two handles below see to that.
+template <class T>
+class DeviceBuf {
+ public:
+  DeviceBuf() = default;
+  DeviceBuf(DeviceBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }   // move-only: no copy, no assignment
+  ~DeviceBuf() { reset(); }
+  hipError_t alloc(size_t n) {   // room for n entries; what it held before is freed first
+    reset();
+    return hipMalloc((void**)&p_, n * sizeof(T));
+  }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+  }
+  T* get() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+};
+
+void fill_objective(lpx_solve_result& r, double v, bool maximize) {
+  if (!maximize) v = -v;                                                            // LPSolver.java:90
+  r.objective = v;
+  lpx_internal::round6_text(v, r.objective_text, sizeof r.objective_text);         // :113
+  r.objective_rounded = strtod(r.objective_text, nullptr);
+}
+
+// The seven scalars a solve kernel answers per LP -- status, phase1_used, x0_slot, n_final (int32), pivots1, pivots2
+// (int64) and v -- as three device arrays of 4, 2 and 1 entries per LP, and their host copies.
+struct SolveScalars {
+  int reserve(size_t count) {
+    HIP_TRY(d_i32.alloc(4 * count));
+    HIP_TRY(d_i64.alloc(2 * count));
+    HIP_TRY(d_v.alloc(count));
+    return 0;
+  }
+  // the seven output fields of a BatchSolveArgs, BatchScenarioArgs or BatchResolveArgs for a launch of `count` LPs
+  template <class Args>
+  void bind(Args& a, int32_t count) {
+    cnt = (size_t)count;
+    a.status = d_i32.get();
+    a.phase1_used = a.status + cnt;
+    a.x0_slot = a.status + 2 * cnt;
+    a.n_final = a.status + 3 * cnt;
+    a.pivots1 = d_i64.get();
+    a.pivots2 = a.pivots1 + cnt;
+    a.v = d_v.get();
+    h_i32.resize(4 * cnt);
+    h_i64.resize(2 * cnt);
+    h_v.resize(cnt);
+  }
+  // what the launch wrote, on the host when this returns
+  int fetch(hipStream_t stream) {
+    HIP_TRY(hipMemcpyAsync(h_i32.data(), d_i32.get(), h_i32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(h_i64.data(), d_i64.get(), h_i64.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(h_v.data(), d_v.get(), h_v.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+  }
+  int32_t n_final(int32_t k) const { return h_i32[3 * cnt + k]; }
+  // LP k's scalars into r (the times are the caller's); true: the kernel reported LPX_DEVICE_ERROR
+  bool decode(int32_t k, bool maximize, lpx_solve_result& r) const {
+    r.status = h_i32[k];
+    r.phase1_used = h_i32[cnt + k];
+    r.x0_slot = h_i32[2 * cnt + k];
+    r.pivots_phase1 = h_i64[k];
+    r.pivots_phase2 = h_i64[cnt + k];
+    fill_objective(r, h_v[k], maximize);
+    return r.status == LPX_DEVICE_ERROR;
+  }
+
+ private:
+  DeviceBuf<int32_t> d_i32;
+  DeviceBuf<int64_t> d_i64;
+  DeviceBuf<double> d_v;
+  std::vector<int32_t> h_i32;
+  std::vector<int64_t> h_i64;
+  std::vector<double> h_v;
+  size_t cnt = 0;   // LPs of the launch bound last
+};
+
+}  // namespace
 
 struct lpx_batch {
   int device = 0;
@@ -30,26 +124,28 @@ struct lpx_batch {
   int32_t threads = 64;             // workgroup size chosen for the batch
   int fused = 0, pricing = 0;
   hipStream_t stream = nullptr;
-  double* d_image = nullptr;
-  int64_t *d_offset = nullptr, *d_pivots = nullptr;
-  int32_t *d_m = nullptr, *d_n = nullptr, *d_status = nullptr, *d_track = nullptr;
+  DeviceBuf<double> d_image;
+  DeviceBuf<int64_t> d_offset, d_pivots;
+  DeviceBuf<int32_t> d_m, d_n, d_status, d_track;
   // lpx_batch_solve
   std::vector<int32_t> n_cur;       // columns of LP k now: n[k], or n[k] + 1 after a solve that ended inside phase 1
   std::vector<int32_t> need_p1;     // minInB of the b given at creation finds a negative entry: the image has room for n + 1 columns
   bool custom_start = false;        // created with a nonzero v or with perm: not the start of LPSolver.solve
   int state = 0;                    // 0: as created, 1: a loop has run, 2: solved
   int32_t solve_threads = 64;       // workgroup size of k_batch_solve: by the auxiliary shape where phase 1 is due
-  // inputs and outputs of k_batch_solve, allocated with the handle: flags, orders, 4 int32 / 2 int64 / 1 double per LP
-  int32_t *d_max = nullptr, *d_p1 = nullptr, *d_order = nullptr, *d_olen = nullptr, *d_si32 = nullptr;
-  int64_t* d_si64 = nullptr;
-  double* d_sv = nullptr;
+  // inputs and outputs of k_batch_solve, allocated with the handle: flags, orders, the seven scalars per LP
+  DeviceBuf<int32_t> d_max, d_p1, d_order, d_olen;
+  SolveScalars scalars;
+
+  // nothing is allocated before the stream exists; the members free themselves after this body
+  ~lpx_batch() {
+    if (!stream) return;
+    (void)hipSetDevice(device);
+    (void)hipStreamDestroy(stream);
+  }
 };
 
 namespace {
-
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 int64_t solve_lds_bytes_of(int64_t m, int64_t n) {
   if (m < 0 || n < 0) return -1;
@@ -127,39 +223,14 @@ int check_forms(const char* who, const Forms& F) {
   return 0;
 }
 
-void free_batch(lpx_batch* B) {
-  if (!B) return;
-  if (B->stream || B->d_image || B->d_offset) {
-    (void)hipSetDevice(B->device);
-    (void)hipFree(B->d_image);
-    (void)hipFree(B->d_offset);
-    (void)hipFree(B->d_pivots);
-    (void)hipFree(B->d_m);
-    (void)hipFree(B->d_n);
-    (void)hipFree(B->d_status);
-    (void)hipFree(B->d_track);
-    (void)hipFree(B->d_max);
-    (void)hipFree(B->d_p1);
-    (void)hipFree(B->d_order);
-    (void)hipFree(B->d_olen);
-    (void)hipFree(B->d_si32);
-    (void)hipFree(B->d_si64);
-    (void)hipFree(B->d_sv);
-    if (B->stream) (void)hipStreamDestroy(B->stream);
-  }
-  delete B;
-}
+using BatchGuard = std::unique_ptr<lpx_batch>;
 
-struct BatchGuard {
-  lpx_batch* B = nullptr;
-  ~BatchGuard() { free_batch(B); }
-};
-
-// the checked core of lpx_batch_create (no argument checks: the callers have made them)
-int create_checked(const Forms& F, const double* v, const int32_t* perm, int device, lpx_batch** out) {
+// the checked core of lpx_batch_create (no argument checks: the callers have made them); a failure leaves `out` empty
+// and nothing allocated
+int create_checked(const Forms& F, const double* v, const int32_t* perm, int device, BatchGuard& out) {
   const int32_t count = F.count, m_max = F.m_max, n_max = F.n_max;
-  BatchGuard guard;
-  lpx_batch* B = guard.B = new lpx_batch();
+  BatchGuard guard(new lpx_batch());
+  lpx_batch* B = guard.get();
   B->device = device;
   B->count = count;
   B->m_max = m_max;
@@ -205,32 +276,35 @@ int create_checked(const Forms& F, const double* v, const int32_t* perm, int dev
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipStreamCreateWithFlags(&B->stream, hipStreamNonBlocking));
   const size_t cnt = (size_t)std::max(count, 1);
-  HIP_TRY(hipMalloc((void**)&B->d_image, std::max<size_t>((size_t)total, 2) * sizeof(double)));
-  HIP_TRY(hipMalloc((void**)&B->d_offset, cnt * sizeof(int64_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_pivots, cnt * sizeof(int64_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_m, cnt * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_n, cnt * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_status, cnt * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_track, cnt * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_max, cnt * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_p1, cnt * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_order, cnt * (size_t)std::max(n_max, 1) * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_olen, cnt * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_si32, 4 * cnt * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_si64, 2 * cnt * sizeof(int64_t)));
-  HIP_TRY(hipMalloc((void**)&B->d_sv, cnt * sizeof(double)));
-  if (total > 0) HIP_TRY(hipMemcpyAsync(B->d_image, img.data(), (size_t)total * sizeof(double), hipMemcpyHostToDevice, B->stream));
+  HIP_TRY(B->d_image.alloc(std::max<size_t>((size_t)total, 2)));
+  HIP_TRY(B->d_offset.alloc(cnt));
+  HIP_TRY(B->d_pivots.alloc(cnt));
+  HIP_TRY(B->d_m.alloc(cnt));
+  HIP_TRY(B->d_n.alloc(cnt));
+  HIP_TRY(B->d_status.alloc(cnt));
+  HIP_TRY(B->d_track.alloc(cnt));
+  HIP_TRY(B->d_max.alloc(cnt));
+  HIP_TRY(B->d_p1.alloc(cnt));
+  HIP_TRY(B->d_order.alloc(cnt * (size_t)std::max(n_max, 1)));
+  HIP_TRY(B->d_olen.alloc(cnt));
+  if (int rc = B->scalars.reserve(cnt)) return rc;
+  if (total > 0) HIP_TRY(hipMemcpyAsync(B->d_image.get(), img.data(), (size_t)total * sizeof(double), hipMemcpyHostToDevice, B->stream));
   if (count > 0) {
-    HIP_TRY(hipMemcpyAsync(B->d_offset, B->offset.data(), (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, B->stream));
-    HIP_TRY(hipMemcpyAsync(B->d_m, B->m.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
-    HIP_TRY(hipMemcpyAsync(B->d_n, B->n.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
-    HIP_TRY(hipMemcpyAsync(B->d_p1, B->need_p1.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+    HIP_TRY(hipMemcpyAsync(B->d_offset.get(), B->offset.data(), (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, B->stream));
+    HIP_TRY(hipMemcpyAsync(B->d_m.get(), B->m.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+    HIP_TRY(hipMemcpyAsync(B->d_n.get(), B->n.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+    HIP_TRY(hipMemcpyAsync(B->d_p1.get(), B->need_p1.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
   }
   HIP_TRY(hipStreamSynchronize(B->stream));   // img goes out of scope
-  guard.B = nullptr;
-  *out = B;
+  out = std::move(guard);
   return 0;
 }
+
+// what a launch asks for; the launch itself and the lpxi_*_launch_info call that describes it read the same one
+struct LaunchShape {
+  int threads;
+  int64_t lds_bytes;
+};
 
 // LPX_BATCH_THREADS (debugging aid of scripts/bench_batch.py, read at every loop call): workgroup size instead of the
 // by-size choice, rounded down to a multiple of 64 inside 64..1024
@@ -251,6 +325,31 @@ int64_t solve_launch_lds(const lpx_batch* B) {
   for (int32_t k = 0; k < B->count; k++)
     lds = std::max(lds, B->need_p1[k] ? solve_lds_bytes_of(B->m[k], B->n[k]) : lds_bytes_of(B->m[k], B->n[k]));
   return lds;
+}
+
+// the launch of lpx_batch_simplex_loop (k_batch_simplex) or of lpx_batch_solve (k_batch_solve) on this handle
+LaunchShape batch_shape(const lpx_batch* B, bool solve) {
+  return {threads_in_effect(B, solve), solve ? solve_launch_lds(B) : B->lds_bytes};
+}
+
+// the launch of a kernel that gives one workgroup an m x n LP of a scenario batch: k_batch_scenarios (phase1: some
+// scenario needs the auxiliary LP, and every workgroup gets its room), k_scenarios_crash and k_batch_resolve (never)
+LaunchShape scenario_shape(int32_t m, int32_t n, bool phase1) {
+  return {threads_or_env(threads_of(m, n + (phase1 ? 1 : 0))),
+          std::max<int64_t>(lpxk::kBatchScratchBytes, phase1 ? solve_lds_bytes_of(m, n) : lds_bytes_of(m, n))};
+}
+
+// threads, LDS bytes and resident workgroups per CU (`occupancy` of the kernel in question) of a launch, into the
+// pointers of an lpxi_*_launch_info call that are not NULL
+template <class Occupancy>
+int report_launch(int device, LaunchShape shape, Occupancy occupancy, int32_t* threads, int32_t* lds_bytes, int32_t* blocks_per_cu) {
+  DeviceRestore keep_device;
+  HIP_TRY(hipSetDevice(device));
+  const int lds = (int)std::min<int64_t>(shape.lds_bytes, INT32_MAX);
+  if (threads) *threads = shape.threads;
+  if (lds_bytes) *lds_bytes = lds;
+  if (blocks_per_cu) *blocks_per_cu = occupancy(shape.threads, lds);
+  return 0;
 }
 
 // one restore order of `len` entries (< 0: n) against an LP with n columns
@@ -276,13 +375,6 @@ int too_large_for_phase1(const char* who, int32_t k, int32_t m, int32_t n) {
   return fail(LPX_BAD_ARGUMENT, msg);
 }
 
-void fill_objective(lpx_solve_result& r, double v, bool maximize) {
-  if (!maximize) v = -v;                                                            // LPSolver.java:90
-  r.objective = v;
-  lpx_internal::round6_text(v, r.objective_text, sizeof r.objective_text);         // :113
-  r.objective_rounded = strtod(r.objective_text, nullptr);
-}
-
 void init_results(lpx_solve_result* results, int32_t count) {
   for (int32_t k = 0; k < count; k++) {
     memset(&results[k], 0, sizeof results[k]);
@@ -305,7 +397,7 @@ int read_images(const lpx_batch* B, std::vector<double>& img) {
   img.resize((size_t)B->offset[B->count]);
   if (img.empty()) return 0;
   HIP_TRY(hipSetDevice(B->device));
-  HIP_TRY(hipMemcpyAsync(img.data(), B->d_image, img.size() * sizeof(double), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipMemcpyAsync(img.data(), B->d_image.get(), img.size() * sizeof(double), hipMemcpyDeviceToHost, B->stream));
   HIP_TRY(hipStreamSynchronize(B->stream));
   return 0;
 }
@@ -330,31 +422,33 @@ void write_solution(const lpx_batch* B, const std::vector<double>& img, int32_t 
 
 int launch_info(const char* who, lpx_batch* B, bool solve, int32_t* threads, int32_t* lds_bytes, int32_t* blocks_per_cu) {
   if (!B) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL handle");
-  DeviceRestore keep_device;
-  HIP_TRY(hipSetDevice(B->device));
-  const int t = threads_in_effect(B, solve);
-  const int lds = solve ? (int)std::min<int64_t>(solve_launch_lds(B), INT32_MAX) : B->lds_bytes;
-  if (threads) *threads = t;
-  if (lds_bytes) *lds_bytes = lds;
-  if (blocks_per_cu) *blocks_per_cu = solve ? lpxk::batch_solve_blocks_per_cu(t, lds) : lpxk::batch_blocks_per_cu(t, lds);
-  return 0;
+  const auto occupancy = solve ? lpxk::batch_solve_blocks_per_cu : lpxk::batch_blocks_per_cu;
+  return report_launch(B->device, batch_shape(B, solve), occupancy, threads, lds_bytes, blocks_per_cu);
 }
 
-// The argument checks of a one-shot call in their order: shapes, arrays, results (and the flags where maximize_due), then
-// the options into `o` (NULL: the defaults) without what a batch cannot honour; `field` is how `who` names those.
-int check_one_shot(const char* who, const Forms& F, bool maximize_due, const lpx_solve_result* results, const char* field,
-                   const lpx_solve_options* opts, lpx_solve_options& o) {
-  if (int rc = check_forms(who, F)) return rc;
-  if (F.count > 0 && (!results || (maximize_due && !F.maximize)))
-    return fail(LPX_BAD_ARGUMENT, std::string(who) + (maximize_due ? ": results or maximize is NULL" : ": results is NULL"));
+// The options of a one-shot call into `o` (NULL: the defaults) without what a batch cannot honour; `field` is how `who`
+// names those.  device_too: a negative device is refused here, beside a bad pricing, and the message says so (the
+// scenario calls refuse it with the matrix, in words of their own).
+int take_options(const char* who, const char* field, bool device_too, const lpx_solve_options* opts, lpx_solve_options& o) {
   o = lpx_solve_options{};
   o.max_pivots = -1;
   if (opts) o = *opts;
   const std::string f(field);
   if (o.keep_state || o.perm_out || o.x_out)
     return fail(LPX_BAD_ARGUMENT, std::string(who) + ": " + f + "keep_state, " + f + "perm_out and " + f + "x_out must be NULL");
-  if (o.device < 0 || (o.pricing != 0 && o.pricing != 1)) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": bad device or pricing");
+  if ((device_too && o.device < 0) || (o.pricing != 0 && o.pricing != 1))
+    return fail(LPX_BAD_ARGUMENT, std::string(who) + (device_too ? ": bad device or pricing" : ": bad pricing"));
   return 0;
+}
+
+// The argument checks of a one-shot batch call in their order: shapes, arrays, results (and the flags where
+// maximize_due), then the options (take_options).
+int check_one_shot(const char* who, const Forms& F, bool maximize_due, const lpx_solve_result* results, const char* field,
+                   const lpx_solve_options* opts, lpx_solve_options& o) {
+  if (int rc = check_forms(who, F)) return rc;
+  if (F.count > 0 && (!results || (maximize_due && !F.maximize)))
+    return fail(LPX_BAD_ARGUMENT, std::string(who) + (maximize_due ? ": results or maximize is NULL" : ": results is NULL"));
+  return take_options(who, field, true, opts, o);
 }
 
 // The forms `index` names, gathered into dense arrays of their own (G): A rows copied from where they are, b and c as
@@ -386,9 +480,9 @@ struct Gathered {
 
   // the handle of the gathered forms, owned by `guard`
   int create(const lpx_solve_options& o, BatchGuard& guard) const {
-    if (int rc = create_checked(G, nullptr, nullptr, o.device, &guard.B)) return rc;
-    guard.B->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
-    guard.B->pricing = o.pricing;
+    if (int rc = create_checked(G, nullptr, nullptr, o.device, guard)) return rc;
+    guard->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
+    guard->pricing = o.pricing;
     return 0;
   }
 };
@@ -431,12 +525,15 @@ extern "C" int lpx_batch_create(int32_t count, int32_t m_max, int32_t n_max, con
   if (int rc = check_forms("lpx_batch_create", F)) return rc;
   if (device < 0) return fail(LPX_BAD_ARGUMENT, "lpx_batch_create: negative device");
   DeviceRestore keep_device;
-  return create_checked(F, v, perm, device, out);
+  BatchGuard B;
+  const int rc = create_checked(F, v, perm, device, B);
+  *out = B.release();
+  return rc;
 }
 
 extern "C" void lpx_batch_destroy(lpx_batch* B) {
   DeviceRestore keep_device;
-  free_batch(B);
+  delete B;
 }
 
 extern "C" int lpx_batch_count(const lpx_batch* B) { return B ? B->count : 0; }
@@ -470,26 +567,27 @@ extern "C" int lpx_batch_simplex_loop(lpx_batch* B, int64_t max_pivots, int64_t*
   HIP_TRY(hipSetDevice(B->device));
   B->state = 1;
   const size_t cnt = (size_t)B->count;
-  if (track_slot) HIP_TRY(hipMemcpyAsync(B->d_track, track_slot, cnt * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
-  else HIP_TRY(hipMemsetAsync(B->d_track, 0xff, cnt * sizeof(int32_t), B->stream));   // -1: nothing tracked
+  if (track_slot) HIP_TRY(hipMemcpyAsync(B->d_track.get(), track_slot, cnt * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+  else HIP_TRY(hipMemsetAsync(B->d_track.get(), 0xff, cnt * sizeof(int32_t), B->stream));   // -1: nothing tracked
+  const LaunchShape shape = batch_shape(B, false);
   lpxk::BatchArgs a{};
   a.count = B->count;
-  a.m = B->d_m;
-  a.n = B->d_n;
-  a.offset = B->d_offset;
-  a.image = B->d_image;
-  a.pivots = B->d_pivots;
-  a.status = B->d_status;
-  a.track = B->d_track;
+  a.m = B->d_m.get();
+  a.n = B->d_n.get();
+  a.offset = B->d_offset.get();
+  a.image = B->d_image.get();
+  a.pivots = B->d_pivots.get();
+  a.status = B->d_status.get();
+  a.track = B->d_track.get();
   a.max_pivots = max_pivots;
   a.dantzig = B->pricing == 1;
   a.fused = B->fused;
-  a.lds_bytes = B->lds_bytes;
-  a.threads = threads_in_effect(B);
+  a.lds_bytes = (int32_t)shape.lds_bytes;
+  a.threads = shape.threads;
   HIP_TRY(lpxk::launch_batch_simplex(a, B->stream));
-  HIP_TRY(hipMemcpyAsync(pivots_done, B->d_pivots, cnt * sizeof(int64_t), hipMemcpyDeviceToHost, B->stream));
-  HIP_TRY(hipMemcpyAsync(status, B->d_status, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, B->stream));
-  if (track_slot) HIP_TRY(hipMemcpyAsync(track_slot, B->d_track, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipMemcpyAsync(pivots_done, B->d_pivots.get(), cnt * sizeof(int64_t), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipMemcpyAsync(status, B->d_status.get(), cnt * sizeof(int32_t), hipMemcpyDeviceToHost, B->stream));
+  if (track_slot) HIP_TRY(hipMemcpyAsync(track_slot, B->d_track.get(), cnt * sizeof(int32_t), hipMemcpyDeviceToHost, B->stream));
   HIP_TRY(hipStreamSynchronize(B->stream));
   return 0;
 }
@@ -503,7 +601,7 @@ extern "C" int lpx_batch_read(lpx_batch* B, int32_t index, double* A, int64_t ld
   std::vector<double> img((size_t)L.image);
   DeviceRestore keep_device;
   HIP_TRY(hipSetDevice(B->device));
-  HIP_TRY(hipMemcpyAsync(img.data(), B->d_image + B->offset[index], img.size() * sizeof(double), hipMemcpyDeviceToHost, B->stream));
+  HIP_TRY(hipMemcpyAsync(img.data(), B->d_image.get() + B->offset[index], img.size() * sizeof(double), hipMemcpyDeviceToHost, B->stream));
   HIP_TRY(hipStreamSynchronize(B->stream));
   if (A && nk > 0)
     for (int32_t i = 0; i < mk; i++) memcpy(A + (int64_t)i * lda, img.data() + (int64_t)i * L.ld, (size_t)nk * sizeof(double));
@@ -552,55 +650,37 @@ extern "C" int lpx_batch_solve(lpx_batch* B, const int32_t* maximize, int64_t ma
   DeviceRestore keep_device;
   HIP_TRY(hipSetDevice(B->device));
   const size_t cnt = (size_t)count;
-  if (maximize) HIP_TRY(hipMemcpyAsync(B->d_max, maximize, cnt * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
-  HIP_TRY(hipMemcpyAsync(B->d_order, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
-  HIP_TRY(hipMemcpyAsync(B->d_olen, olen.data(), cnt * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+  if (maximize) HIP_TRY(hipMemcpyAsync(B->d_max.get(), maximize, cnt * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+  HIP_TRY(hipMemcpyAsync(B->d_order.get(), order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+  HIP_TRY(hipMemcpyAsync(B->d_olen.get(), olen.data(), cnt * sizeof(int32_t), hipMemcpyHostToDevice, B->stream));
+  const LaunchShape shape = batch_shape(B, true);
   lpxk::BatchSolveArgs a{};
   a.count = count;
-  a.m = B->d_m;
-  a.n = B->d_n;
-  a.offset = B->d_offset;
-  a.image = B->d_image;
-  a.maximize = maximize ? B->d_max : nullptr;
-  a.phase1 = B->d_p1;
-  a.order = B->d_order;
-  a.order_len = B->d_olen;
+  a.m = B->d_m.get();
+  a.n = B->d_n.get();
+  a.offset = B->d_offset.get();
+  a.image = B->d_image.get();
+  a.maximize = maximize ? B->d_max.get() : nullptr;
+  a.phase1 = B->d_p1.get();
+  a.order = B->d_order.get();
+  a.order_len = B->d_olen.get();
   a.order_pitch = pitch;
-  a.status = B->d_si32;
-  a.phase1_used = a.status + cnt;
-  a.x0_slot = a.status + 2 * cnt;
-  a.n_final = a.status + 3 * cnt;
-  a.pivots1 = B->d_si64;
-  a.pivots2 = a.pivots1 + cnt;
-  a.v = B->d_sv;
+  B->scalars.bind(a, count);
   a.max_pivots = max_pivots < 0 ? -1 : max_pivots;
   a.dantzig = B->pricing == 1;
   a.fused = B->fused;
-  a.lds_bytes = (int32_t)solve_launch_lds(B);
-  a.threads = threads_in_effect(B, true);
+  a.lds_bytes = (int32_t)shape.lds_bytes;
+  a.threads = shape.threads;
   B->state = 2;
-  std::vector<int32_t> h_i32(4 * cnt);
-  std::vector<int64_t> h_i64(2 * cnt);
-  std::vector<double> h_v(cnt);
-  const double t0 = now_s();
+  const double t0 = now_s();   // behind uploads that may still be on their way: they count
   HIP_TRY(lpxk::launch_batch_solve(a, B->stream));
   HIP_TRY(hipStreamSynchronize(B->stream));
   const double t_pivots = now_s() - t0;
-  HIP_TRY(hipMemcpyAsync(h_i32.data(), B->d_si32, h_i32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, B->stream));
-  HIP_TRY(hipMemcpyAsync(h_i64.data(), B->d_si64, h_i64.size() * sizeof(int64_t), hipMemcpyDeviceToHost, B->stream));
-  HIP_TRY(hipMemcpyAsync(h_v.data(), B->d_sv, h_v.size() * sizeof(double), hipMemcpyDeviceToHost, B->stream));
-  HIP_TRY(hipStreamSynchronize(B->stream));
+  if (int rc = B->scalars.fetch(B->stream)) return rc;
   bool device_error = false;
   for (int32_t k = 0; k < count; k++) {
-    lpx_solve_result& r = results[k];
-    r.status = h_i32[k];
-    r.phase1_used = h_i32[cnt + k];
-    r.x0_slot = h_i32[2 * cnt + k];
-    B->n_cur[k] = h_i32[3 * cnt + k];
-    r.pivots_phase1 = h_i64[k];
-    r.pivots_phase2 = h_i64[cnt + k];
-    fill_objective(r, h_v[k], !maximize || maximize[k] != 0);
-    device_error |= r.status == LPX_DEVICE_ERROR;
+    device_error |= B->scalars.decode(k, !maximize || maximize[k] != 0, results[k]);
+    B->n_cur[k] = B->scalars.n_final(k);
   }
   stamp_seconds(results, count, t_start, t_pivots);
   if (device_error) return fail(LPX_DEVICE_ERROR, "lpx_batch_solve: the kernel and the host disagree about an LP's layout");
@@ -650,11 +730,11 @@ extern "C" int lpx_solve_batch(int32_t count, int32_t m_max, int32_t n_max, cons
     DeviceRestore keep_device;
     BatchGuard guard;
     if (int rc = G.create(o, guard)) return rc;
-    const lpx_batch* B = guard.B;
+    const lpx_batch* B = guard.get();
     std::vector<int64_t> done(nb);
     std::vector<int32_t> st(nb);
     const double t0 = now_s();
-    if (int rc = lpx_batch_simplex_loop(guard.B, o.max_pivots < 0 ? -1 : o.max_pivots, done.data(), st.data(), nullptr)) return rc;
+    if (int rc = lpx_batch_simplex_loop(guard.get(), o.max_pivots < 0 ? -1 : o.max_pivots, done.data(), st.data(), nullptr)) return rc;
     t_pivots = now_s() - t0;
     std::vector<double> img;
     if (int rc = read_images(B, img)) return rc;
@@ -710,7 +790,7 @@ extern "C" int lpx_solve_batch_all(int32_t count, int32_t m_max, int32_t n_max, 
     DeviceRestore keep_device;
     BatchGuard guard;
     if (int rc = G.create(o, guard)) return rc;
-    lpx_batch* B = guard.B;
+    lpx_batch* B = guard.get();
     std::vector<lpx_solve_result> res(nb);
     if (int rc = lpx_batch_solve(B, bmax.data(), o.max_pivots, o.restore_order ? border.data() : nullptr,
                                  o.restore_order ? blen.data() : nullptr, res.data()))
@@ -739,59 +819,30 @@ struct lpx_scenarios {
   int32_t m = 0, n = 0;
   int fused = 0, pricing = 0;
   hipStream_t stream = nullptr;
-  double* d_A = nullptr;
+  DeviceBuf<double> d_A;
+  DeviceBuf<int32_t> d_order;
   int32_t cap = 0;   // scenarios the buffers below hold
-  double *d_b = nullptr, *d_c = nullptr, *d_sv = nullptr, *d_x = nullptr;
-  int32_t *d_flags = nullptr, *d_order = nullptr, *d_si32 = nullptr, *d_perm = nullptr;
-  int64_t* d_si64 = nullptr;
+  DeviceBuf<double> d_b, d_c, d_x;
+  DeviceBuf<int32_t> d_flags, d_perm;
+  SolveScalars scalars;
   // re-solve from a shared basis (lpx_scenarios_set_basis): the eta file of the crash, the matrix and the permutation at
   // the basis; per scenario the route k_batch_resolve took
   bool has_basis = false;
   int32_t n_eta = 0;
-  double *d_eta = nullptr, *d_A_basis = nullptr;
-  int32_t *d_perm_basis = nullptr, *d_wanted = nullptr, *d_info = nullptr, *d_route = nullptr;
+  DeviceBuf<double> d_eta, d_A_basis;
+  DeviceBuf<int32_t> d_perm_basis, d_wanted, d_info, d_route;   // d_route: per scenario, sized with the buffers under `cap`
+
+  // nothing is allocated before the stream exists; the members free themselves after this body
+  ~lpx_scenarios() {
+    if (!stream) return;
+    (void)hipSetDevice(device);
+    (void)hipStreamDestroy(stream);
+  }
 };
 
 namespace {
 
-void free_scenario_buffers(lpx_scenarios* S) {
-  (void)hipFree(S->d_route);
-  S->d_route = nullptr;
-  (void)hipFree(S->d_b);
-  (void)hipFree(S->d_c);
-  (void)hipFree(S->d_sv);
-  (void)hipFree(S->d_x);
-  (void)hipFree(S->d_flags);
-  (void)hipFree(S->d_si32);
-  (void)hipFree(S->d_perm);
-  (void)hipFree(S->d_si64);
-  S->d_b = S->d_c = S->d_sv = S->d_x = nullptr;
-  S->d_flags = S->d_si32 = S->d_perm = nullptr;
-  S->d_si64 = nullptr;
-  S->cap = 0;
-}
-
-void free_scenarios(lpx_scenarios* S) {
-  if (!S) return;
-  if (S->stream || S->d_A) {
-    (void)hipSetDevice(S->device);
-    free_scenario_buffers(S);
-    (void)hipFree(S->d_A);
-    (void)hipFree(S->d_order);
-    (void)hipFree(S->d_eta);
-    (void)hipFree(S->d_A_basis);
-    (void)hipFree(S->d_perm_basis);
-    (void)hipFree(S->d_wanted);
-    (void)hipFree(S->d_info);
-    if (S->stream) (void)hipStreamDestroy(S->stream);
-  }
-  delete S;
-}
-
-struct ScenariosGuard {
-  lpx_scenarios* S = nullptr;
-  ~ScenariosGuard() { free_scenarios(S); }
-};
+using ScenariosGuard = std::unique_ptr<lpx_scenarios>;
 
 // the shape and the matrix of a scenario batch
 int check_scenario_matrix(const char* who, int32_t m, int32_t n, const double* A, int64_t lda, int device) {
@@ -809,21 +860,39 @@ int check_scenario_matrix(const char* who, int32_t m, int32_t n, const double* A
   return 0;
 }
 
-// the arguments of one solve on an m x n matrix; fills flags[count]: bit 0 = maximise, bit 1 = minInB (LPSolver.java:375-386,
-// the rule of Forms::phase1) finds a negative entry in the scenario's b.  *any_p1: some scenario needs the auxiliary LP.
-int check_scenario_solve(const char* who, int32_t m, int32_t n, int32_t count, const double* b, int64_t ldb, const double* c,
-                         int64_t ldc, const int32_t* maximize, const int32_t* order, int32_t order_len,
-                         const lpx_solve_result* results, std::vector<int32_t>& flags, bool* any_p1) {
+// A solve or a re-solve as the ABI passes it: `count` scenarios, b and c at their pitches (0: one vector), the budget,
+// the restore order (NULL: the default) and where the answers go (x_out, perm_out: NULL for none); then what
+// check_scenario_solve makes of it
+struct ScenarioCall {
+  int32_t count;
+  const double *b, *c;
+  int64_t ldb, ldc;
+  int64_t max_pivots;
+  const int32_t* restore_order;
+  int32_t restore_order_len;
+  lpx_solve_result* results;
+  double* x_out;
+  int32_t* perm_out;
+  std::vector<int32_t> flags;   // [count] bit 0 = maximise, bit 1 = the scenario needs the auxiliary LP
+  bool any_p1 = false;          // some scenario does
+};
+
+// the arguments of one solve on an m x n matrix; fills call.flags -- bit 1: minInB (LPSolver.java:375-386, the rule of
+// Forms::phase1) finds a negative entry in the scenario's b -- and call.any_p1
+int check_scenario_solve(const char* who, int32_t m, int32_t n, const int32_t* maximize, ScenarioCall& call) {
+  const int32_t count = call.count;
+  const double* b = call.b;
+  const int64_t ldb = call.ldb;
   if (count < 0) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": negative count");
   if (ldb != 0 && ldb < m) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": ldb is neither 0 nor >= m");
-  if (ldc != 0 && ldc < n) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": ldc is neither 0 nor >= n");
-  if (count > 0 && !results) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": results is NULL");
-  if (count > 0 && ((m > 0 && !b) || (n > 0 && !c)))
+  if (call.ldc != 0 && call.ldc < n) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": ldc is neither 0 nor >= n");
+  if (count > 0 && !call.results) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": results is NULL");
+  if (count > 0 && ((m > 0 && !b) || (n > 0 && !call.c)))
     return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL array where data is due (b or c)");
-  if (order)
-    if (int rc = check_order(who, 0, m, n, order, order_len)) return rc;
-  flags.assign((size_t)std::max(count, 0), 0);
-  *any_p1 = false;
+  if (call.restore_order)
+    if (int rc = check_order(who, 0, m, n, call.restore_order, call.restore_order_len)) return rc;
+  call.flags.assign((size_t)std::max(count, 0), 0);
+  call.any_p1 = false;
   const bool aux_fits = solve_lds_bytes_of(m, n) <= LPX_BATCH_LDS_BYTES;
   for (int32_t k = 0; k < count; k++) {
     const double* bk = b ? b + (int64_t)k * ldb : nullptr;
@@ -835,45 +904,44 @@ int check_scenario_solve(const char* who, int32_t m, int32_t n, int32_t count, c
                who, k, m, n, (long long)solve_lds_bytes_of(m, n), LPX_BATCH_LDS_BYTES);
       return fail(LPX_BAD_ARGUMENT, msg);
     }
-    *any_p1 |= p1;
-    flags[k] = (!maximize || maximize[k] != 0 ? 1 : 0) | (p1 ? 2 : 0);
+    call.any_p1 |= p1;
+    call.flags[k] = (!maximize || maximize[k] != 0 ? 1 : 0) | (p1 ? 2 : 0);
   }
   return 0;
 }
 
-int scenarios_create_checked(int32_t m, int32_t n, const double* A, int64_t lda, int device, lpx_scenarios** out) {
-  ScenariosGuard guard;
-  lpx_scenarios* S = guard.S = new lpx_scenarios();
+// a failure leaves `out` empty and nothing allocated
+int scenarios_create_checked(int32_t m, int32_t n, const double* A, int64_t lda, int device, ScenariosGuard& out) {
+  ScenariosGuard guard(new lpx_scenarios());
+  lpx_scenarios* S = guard.get();
   S->device = device;
   S->m = m;
   S->n = n;
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
-  HIP_TRY(hipMalloc((void**)&S->d_A, std::max<size_t>((size_t)m * n, 1) * sizeof(double)));
-  HIP_TRY(hipMalloc((void**)&S->d_order, (size_t)std::max(n, 1) * sizeof(int32_t)));
+  HIP_TRY(S->d_A.alloc(std::max<size_t>((size_t)m * n, 1)));
+  HIP_TRY(S->d_order.alloc((size_t)std::max(n, 1)));
   if (m > 0 && n > 0) {
-    HIP_TRY(hipMemcpy2DAsync(S->d_A, (size_t)n * sizeof(double), A, (size_t)lda * sizeof(double), (size_t)n * sizeof(double),
+    HIP_TRY(hipMemcpy2DAsync(S->d_A.get(), (size_t)n * sizeof(double), A, (size_t)lda * sizeof(double), (size_t)n * sizeof(double),
                              (size_t)m, hipMemcpyHostToDevice, S->stream));
     HIP_TRY(hipStreamSynchronize(S->stream));   // the caller's A is free again
   }
-  guard.S = nullptr;
-  *out = S;
+  out = std::move(guard);
   return 0;
 }
 
+// room for `count` scenarios: the per-scenario buffers grow to the largest count seen
 int scenarios_reserve(lpx_scenarios* S, int32_t count) {
   if (count <= S->cap) return 0;
-  free_scenario_buffers(S);
+  S->cap = 0;   // until every buffer has its new size
   const size_t cnt = (size_t)count, m = (size_t)S->m, n = (size_t)S->n;
-  HIP_TRY(hipMalloc((void**)&S->d_b, std::max<size_t>(cnt * m, 1) * sizeof(double)));
-  HIP_TRY(hipMalloc((void**)&S->d_c, std::max<size_t>(cnt * n, 1) * sizeof(double)));
-  HIP_TRY(hipMalloc((void**)&S->d_sv, cnt * sizeof(double)));
-  HIP_TRY(hipMalloc((void**)&S->d_x, std::max<size_t>(cnt * n, 1) * sizeof(double)));
-  HIP_TRY(hipMalloc((void**)&S->d_flags, cnt * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&S->d_si32, 4 * cnt * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&S->d_perm, std::max<size_t>(cnt * (n + m), 1) * sizeof(int32_t)));
-  HIP_TRY(hipMalloc((void**)&S->d_si64, 2 * cnt * sizeof(int64_t)));
-  HIP_TRY(hipMalloc((void**)&S->d_route, cnt * sizeof(int32_t)));
+  HIP_TRY(S->d_b.alloc(std::max<size_t>(cnt * m, 1)));
+  HIP_TRY(S->d_c.alloc(std::max<size_t>(cnt * n, 1)));
+  HIP_TRY(S->d_x.alloc(std::max<size_t>(cnt * n, 1)));
+  HIP_TRY(S->d_flags.alloc(cnt));
+  HIP_TRY(S->d_perm.alloc(std::max<size_t>(cnt * (n + m), 1)));
+  HIP_TRY(S->d_route.alloc(cnt));
+  if (int rc = S->scalars.reserve(cnt)) return rc;
   S->cap = count;
   return 0;
 }
@@ -888,103 +956,101 @@ int upload_vectors(lpx_scenarios* S, double* dst, const double* src, int64_t ld,
   return 0;
 }
 
-// the checked core of lpx_scenarios_solve: flags and any_p1 from check_scenario_solve, count > 0
-int scenarios_solve_checked(const char* who, lpx_scenarios* S, int32_t count, const double* b, int64_t ldb, const double* c,
-                            int64_t ldc, const std::vector<int32_t>& flags, bool any_p1, int64_t max_pivots,
-                            const int32_t* restore_order, int32_t restore_order_len, lpx_solve_result* results, double* x_out,
-                            int32_t* perm_out) {
-  const double t_start = now_s();
-  const int32_t m = S->m, n = S->n;
-  std::vector<int32_t> order((size_t)std::max(n, 1), 0);
-  int32_t olen = n;
-  if (restore_order) {
-    olen = restore_order_len < 0 ? n : restore_order_len;
-    std::copy(restore_order, restore_order + olen, order.begin());
-  } else if (n > 0) {
-    lpx_java_default_name_order(n, order.data());
-  }
-  init_results(results, count);
+// What lpx_scenarios_solve and lpx_scenarios_resolve do alike, up to the end of their launch.  Room for the call's
+// scenarios; b, c and the flags go up, and the a.order_len entries of `order` where the kernel reads a restore order.
+// The fields of `a` that every scenario kernel reads are set here; A and what only one kernel reads are the caller's.
+// Then `launch` alone between two synchronises: t_pivots is the seconds of that window.
+template <class Args, class Launch>
+int launch_scenarios(lpx_scenarios* S, const ScenarioCall& call, Args& a, LaunchShape shape, const int32_t* order, Launch launch,
+                     double& t_pivots) {
+  const int32_t m = S->m, n = S->n, count = call.count;
   HIP_TRY(hipSetDevice(S->device));
   if (int rc = scenarios_reserve(S, count)) return rc;
-  const size_t cnt = (size_t)count;
-  if (int rc = upload_vectors(S, S->d_b, b, ldb, m, count)) return rc;
-  if (int rc = upload_vectors(S, S->d_c, c, ldc, n, count)) return rc;
-  HIP_TRY(hipMemcpyAsync(S->d_flags, flags.data(), cnt * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
-  if (olen > 0) HIP_TRY(hipMemcpyAsync(S->d_order, order.data(), (size_t)olen * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
-  lpxk::BatchScenarioArgs a{};
+  if (int rc = upload_vectors(S, S->d_b.get(), call.b, call.ldb, m, count)) return rc;
+  if (int rc = upload_vectors(S, S->d_c.get(), call.c, call.ldc, n, count)) return rc;
+  HIP_TRY(hipMemcpyAsync(S->d_flags.get(), call.flags.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
+  if (a.order_len > 0)
+    HIP_TRY(hipMemcpyAsync(S->d_order.get(), order, (size_t)a.order_len * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
   a.count = count;
   a.m = m;
   a.n = n;
-  a.A = S->d_A;
-  a.b = S->d_b;
-  a.c = S->d_c;
-  a.ldb = ldb == 0 ? 0 : m;
-  a.ldc = ldc == 0 ? 0 : n;
-  a.flags = S->d_flags;
-  a.order = S->d_order;
-  a.order_len = olen;
-  a.status = S->d_si32;
-  a.phase1_used = a.status + cnt;
-  a.x0_slot = a.status + 2 * cnt;
-  a.n_final = a.status + 3 * cnt;
-  a.pivots1 = S->d_si64;
-  a.pivots2 = a.pivots1 + cnt;
-  a.v = S->d_sv;
-  a.x_out = x_out ? S->d_x : nullptr;
-  a.perm_out = perm_out ? S->d_perm : nullptr;
-  a.max_pivots = max_pivots < 0 ? -1 : max_pivots;
+  a.b = S->d_b.get();
+  a.c = S->d_c.get();
+  a.ldb = call.ldb == 0 ? 0 : m;
+  a.ldc = call.ldc == 0 ? 0 : n;
+  a.flags = S->d_flags.get();
+  S->scalars.bind(a, count);
+  a.x_out = call.x_out ? S->d_x.get() : nullptr;
+  a.perm_out = call.perm_out ? S->d_perm.get() : nullptr;
+  a.max_pivots = call.max_pivots < 0 ? -1 : call.max_pivots;
   a.dantzig = S->pricing == 1;
   a.fused = S->fused;
-  a.lds_bytes = (int32_t)std::max<int64_t>(lpxk::kBatchScratchBytes, any_p1 ? solve_lds_bytes_of(m, n) : lds_bytes_of(m, n));
-  a.threads = threads_or_env(threads_of(m, n + (any_p1 ? 1 : 0)));
-  std::vector<int32_t> h_i32(4 * cnt);
-  std::vector<int64_t> h_i64(2 * cnt);
-  std::vector<double> h_v(cnt);
+  a.lds_bytes = (int32_t)shape.lds_bytes;
+  a.threads = shape.threads;
   HIP_TRY(hipStreamSynchronize(S->stream));   // the uploads are through: seconds_pivots is the launch alone
   const double t0 = now_s();
-  HIP_TRY(lpxk::launch_batch_scenarios(a, S->stream));
+  HIP_TRY(launch());
   HIP_TRY(hipStreamSynchronize(S->stream));
-  const double t_pivots = now_s() - t0;
-  HIP_TRY(hipMemcpyAsync(h_i32.data(), S->d_si32, h_i32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-  HIP_TRY(hipMemcpyAsync(h_i64.data(), S->d_si64, h_i64.size() * sizeof(int64_t), hipMemcpyDeviceToHost, S->stream));
-  HIP_TRY(hipMemcpyAsync(h_v.data(), S->d_sv, h_v.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+  t_pivots = now_s() - t0;
+  return 0;
+}
+
+// row t of xs (pitch xw) and of ps (pitch pw) into row k of x_out and perm_out; a NULL source is not wanted
+void copy_row(size_t xw, size_t pw, const double* xs, const int32_t* ps, size_t t, double* x_out, int32_t* perm_out, size_t k) {
+  if (xs && xw > 0) memcpy(x_out + k * xw, xs + t * xw, xw * sizeof(double));
+  if (ps && pw > 0) memcpy(perm_out + k * pw, ps + t * pw, pw * sizeof(int32_t));
+}
+
+// x and perm of the scenarios k with keep(k), from the rows the kernel wrote on the device, into the caller's x_out and
+// perm_out (either may be NULL).  All of them (the usual case): one copy each straight into the caller's arrays; else
+// through a host copy, row by row, and the rows of the others stay as they are
+template <class Keep>
+int download_rows(lpx_scenarios* S, int32_t count, Keep keep, double* x_out, int32_t* perm_out) {
+  const size_t cnt = (size_t)count, xw = (size_t)S->n, pw = (size_t)S->n + S->m;
+  bool all = true;
+  for (int32_t k = 0; k < count; k++) all &= keep(k);
+  std::vector<double> hx(!all && x_out ? cnt * xw : 0);
+  std::vector<int32_t> hp(!all && perm_out ? cnt * pw : 0);
+  if (x_out && xw > 0)
+    HIP_TRY(hipMemcpyAsync(all ? x_out : hx.data(), S->d_x.get(), cnt * xw * sizeof(double), hipMemcpyDeviceToHost, S->stream));
+  if (perm_out && pw > 0)
+    HIP_TRY(hipMemcpyAsync(all ? perm_out : hp.data(), S->d_perm.get(), cnt * pw * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
   HIP_TRY(hipStreamSynchronize(S->stream));
-  bool device_error = false, all_mxn = true;
-  for (int32_t k = 0; k < count; k++) {
-    lpx_solve_result& r = results[k];
-    r.status = h_i32[k];
-    r.phase1_used = h_i32[cnt + k];
-    r.x0_slot = h_i32[2 * cnt + k];
-    r.pivots_phase1 = h_i64[k];
-    r.pivots_phase2 = h_i64[cnt + k];
-    fill_objective(r, h_v[k], (flags[k] & 1) != 0);
-    device_error |= r.status == LPX_DEVICE_ERROR;
-    all_mxn &= h_i32[3 * cnt + k] == n;
+  for (int32_t k = 0; !all && k < count; k++)
+    if (keep(k)) copy_row(xw, pw, x_out ? hx.data() : nullptr, perm_out ? hp.data() : nullptr, k, x_out, perm_out, k);
+  return 0;
+}
+
+// the checked core of lpx_scenarios_solve: count > 0
+int scenarios_solve_checked(const char* who, lpx_scenarios* S, const ScenarioCall& call) {
+  const double t_start = now_s();
+  const int32_t m = S->m, n = S->n, count = call.count;
+  std::vector<int32_t> order((size_t)std::max(n, 1), 0);
+  lpxk::BatchScenarioArgs a{};
+  a.A = S->d_A.get();
+  a.order = S->d_order.get();
+  a.order_len = n;
+  if (call.restore_order) {
+    a.order_len = call.restore_order_len < 0 ? n : call.restore_order_len;
+    std::copy(call.restore_order, call.restore_order + a.order_len, order.begin());
+  } else if (n > 0) {
+    lpx_java_default_name_order(n, order.data());
   }
+  init_results(call.results, count);
+  double t_pivots = 0.0;
+  auto launch = [&] { return lpxk::launch_batch_scenarios(a, S->stream); };
+  if (int rc = launch_scenarios(S, call, a, scenario_shape(m, n, call.any_p1), order.data(), launch, t_pivots)) return rc;
+  if (int rc = S->scalars.fetch(S->stream)) return rc;
+  bool device_error = false;
+  for (int32_t k = 0; k < count; k++) device_error |= S->scalars.decode(k, (call.flags[k] & 1) != 0, call.results[k]);
   if (device_error) {
-    stamp_seconds(results, count, t_start, t_pivots);
+    stamp_seconds(call.results, count, t_start, t_pivots);
     return fail(LPX_DEVICE_ERROR, std::string(who) + ": the kernel and the host disagree about a scenario's layout");
   }
-  // x and perm: the kernel wrote the rows of the scenarios that ended m x n and no others.  All of them (the usual
-  // case): one copy each into the caller's arrays; else through a host copy, row by row
-  const size_t xw = (size_t)n, pw = (size_t)n + m;
-  if (all_mxn) {
-    if (x_out && xw > 0) HIP_TRY(hipMemcpyAsync(x_out, S->d_x, cnt * xw * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-    if (perm_out && pw > 0) HIP_TRY(hipMemcpyAsync(perm_out, S->d_perm, cnt * pw * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-    HIP_TRY(hipStreamSynchronize(S->stream));
-  } else {
-    std::vector<double> hx(x_out ? cnt * xw : 0);
-    std::vector<int32_t> hp(perm_out ? cnt * pw : 0);
-    if (!hx.empty()) HIP_TRY(hipMemcpyAsync(hx.data(), S->d_x, hx.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-    if (!hp.empty()) HIP_TRY(hipMemcpyAsync(hp.data(), S->d_perm, hp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-    HIP_TRY(hipStreamSynchronize(S->stream));
-    for (int32_t k = 0; k < count; k++) {
-      if (h_i32[3 * cnt + k] != n) continue;
-      if (!hx.empty()) memcpy(x_out + k * xw, hx.data() + k * xw, xw * sizeof(double));
-      if (!hp.empty()) memcpy(perm_out + k * pw, hp.data() + k * pw, pw * sizeof(int32_t));
-    }
-  }
-  stamp_seconds(results, count, t_start, t_pivots);
+  // the kernel wrote the rows of the scenarios that ended m x n and no others
+  auto ended_mxn = [&](int32_t k) { return S->scalars.n_final(k) == n; };
+  if (int rc = download_rows(S, count, ended_mxn, call.x_out, call.perm_out)) return rc;
+  stamp_seconds(call.results, count, t_start, t_pivots);
   return 0;
 }
 
@@ -1018,31 +1084,32 @@ int scenarios_set_basis_checked(const char* who, lpx_scenarios* S, const int32_t
   std::vector<int32_t> wanted((size_t)std::max(n + m, 1), 0);
   for (int32_t i = 0; i < m; i++) wanted[basis[i]] = 1;
   HIP_TRY(hipSetDevice(S->device));
-  if (!S->d_eta) {
+  if (!S->d_eta.get()) {
     const size_t etas = (size_t)std::min(m, n) * (size_t)lpxk::eta_stride(m, n);
-    HIP_TRY(hipMalloc((void**)&S->d_eta, std::max<size_t>(etas, 1) * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&S->d_A_basis, std::max<size_t>((size_t)m * n, 1) * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&S->d_perm_basis, wanted.size() * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void**)&S->d_wanted, wanted.size() * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void**)&S->d_info, 2 * sizeof(int32_t)));
+    HIP_TRY(S->d_eta.alloc(std::max<size_t>(etas, 1)));
+    HIP_TRY(S->d_A_basis.alloc(std::max<size_t>((size_t)m * n, 1)));
+    HIP_TRY(S->d_perm_basis.alloc(wanted.size()));
+    HIP_TRY(S->d_wanted.alloc(wanted.size()));
+    HIP_TRY(S->d_info.alloc(2));
   }
-  HIP_TRY(hipMemcpyAsync(S->d_wanted, wanted.data(), wanted.size() * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
+  HIP_TRY(hipMemcpyAsync(S->d_wanted.get(), wanted.data(), wanted.size() * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
+  const LaunchShape shape = scenario_shape(m, n, false);
   lpxk::ScenarioCrashArgs a{};
   a.count = 1;
   a.m = m;
   a.n = n;
-  a.A = S->d_A;
-  a.wanted = S->d_wanted;
-  a.A_out = S->d_A_basis;
-  a.perm_out = S->d_perm_basis;
-  a.eta = S->d_eta;
-  a.info = S->d_info;
+  a.A = S->d_A.get();
+  a.wanted = S->d_wanted.get();
+  a.A_out = S->d_A_basis.get();
+  a.perm_out = S->d_perm_basis.get();
+  a.eta = S->d_eta.get();
+  a.info = S->d_info.get();
   a.fused = S->fused;
-  a.lds_bytes = (int32_t)std::max<int64_t>(lpxk::kBatchScratchBytes, lds_bytes_of(m, n));
-  a.threads = threads_or_env(threads_of(m, n));
+  a.lds_bytes = (int32_t)shape.lds_bytes;
+  a.threads = shape.threads;
   HIP_TRY(lpxk::launch_scenarios_crash(a, S->stream));
   int32_t info[2] = {0, -2};
-  HIP_TRY(hipMemcpyAsync(info, S->d_info, sizeof info, hipMemcpyDeviceToHost, S->stream));
+  HIP_TRY(hipMemcpyAsync(info, S->d_info.get(), sizeof info, hipMemcpyDeviceToHost, S->stream));
   HIP_TRY(hipStreamSynchronize(S->stream));
   if (info[1] == -2) return fail(LPX_DEVICE_ERROR, std::string(who) + ": the kernel and the host disagree about the layout");
   if (info[1] >= 0) {
@@ -1056,130 +1123,100 @@ int scenarios_set_basis_checked(const char* who, lpx_scenarios* S, const int32_t
   return 0;
 }
 
-// the checked core of lpx_scenarios_resolve: flags from check_scenario_solve, count > 0, the handle has a basis
-int scenarios_resolve_checked(const char* who, lpx_scenarios* S, int32_t count, const double* b, int64_t ldb, const double* c,
-                              int64_t ldc, const std::vector<int32_t>& flags, int64_t max_pivots, const int32_t* restore_order,
-                              int32_t restore_order_len, lpx_solve_result* results, double* x_out, int32_t* perm_out,
-                              int32_t* route_out) {
-  const double t_start = now_s();
+// The scenarios k_batch_resolve routed cold (none: nothing to do): lpx_scenarios_solve on their rows of b and c,
+// gathered; results, x and perm scattered back, and the seconds of that launch added to t_pivots
+int resolve_cold(const char* who, lpx_scenarios* S, const ScenarioCall& call, const std::vector<int32_t>& route, double& t_pivots) {
   const int32_t m = S->m, n = S->n;
-  init_results(results, count);
-  HIP_TRY(hipSetDevice(S->device));
-  if (int rc = scenarios_reserve(S, count)) return rc;
-  const size_t cnt = (size_t)count;
-  if (int rc = upload_vectors(S, S->d_b, b, ldb, m, count)) return rc;
-  if (int rc = upload_vectors(S, S->d_c, c, ldc, n, count)) return rc;
-  HIP_TRY(hipMemcpyAsync(S->d_flags, flags.data(), cnt * sizeof(int32_t), hipMemcpyHostToDevice, S->stream));
-  lpxk::BatchResolveArgs a{};
-  a.count = count;
-  a.m = m;
-  a.n = n;
-  a.A = S->d_A_basis;
-  a.b = S->d_b;
-  a.c = S->d_c;
-  a.ldb = ldb == 0 ? 0 : m;
-  a.ldc = ldc == 0 ? 0 : n;
-  a.flags = S->d_flags;
-  a.status = S->d_si32;
-  a.phase1_used = a.status + cnt;
-  a.x0_slot = a.status + 2 * cnt;
-  a.n_final = a.status + 3 * cnt;
-  a.pivots1 = S->d_si64;
-  a.pivots2 = a.pivots1 + cnt;
-  a.v = S->d_sv;
-  a.x_out = x_out ? S->d_x : nullptr;
-  a.perm_out = perm_out ? S->d_perm : nullptr;
-  a.max_pivots = max_pivots < 0 ? -1 : max_pivots;
-  a.dantzig = S->pricing == 1;
-  a.fused = S->fused;
-  a.lds_bytes = (int32_t)std::max<int64_t>(lpxk::kBatchScratchBytes, lds_bytes_of(m, n));
-  a.threads = threads_or_env(threads_of(m, n));
-  a.perm0 = S->d_perm_basis;
-  a.eta = S->d_eta;
-  a.n_eta = S->n_eta;
-  a.route = S->d_route;
-  std::vector<int32_t> h_route(cnt), h_i32(4 * cnt);
-  std::vector<int64_t> h_i64(2 * cnt);
-  std::vector<double> h_v(cnt);
-  HIP_TRY(hipStreamSynchronize(S->stream));   // the uploads are through: seconds_pivots is the launches alone
-  const double t0 = now_s();
-  HIP_TRY(lpxk::launch_batch_resolve(a, S->stream));
-  HIP_TRY(hipStreamSynchronize(S->stream));
-  double t_pivots = now_s() - t0;
-  HIP_TRY(hipMemcpyAsync(h_route.data(), S->d_route, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-  HIP_TRY(hipMemcpyAsync(h_i32.data(), S->d_si32, h_i32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-  HIP_TRY(hipMemcpyAsync(h_i64.data(), S->d_si64, h_i64.size() * sizeof(int64_t), hipMemcpyDeviceToHost, S->stream));
-  HIP_TRY(hipMemcpyAsync(h_v.data(), S->d_sv, h_v.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-  HIP_TRY(hipStreamSynchronize(S->stream));
+  const int64_t ldb = call.ldb, ldc = call.ldc;
+  const size_t xw = (size_t)n, pw = (size_t)n + m;
   std::vector<int32_t> cold;
-  bool device_error = false;
-  for (int32_t k = 0; k < count; k++) {
-    if (h_route[k] == LPX_ROUTE_COLD) {
-      cold.push_back(k);
-      continue;
-    }
-    lpx_solve_result& r = results[k];
-    r.status = h_i32[k];
-    r.phase1_used = 0;
-    r.x0_slot = -1;
-    r.pivots_phase1 = h_i64[k];
-    r.pivots_phase2 = h_i64[cnt + k];
-    fill_objective(r, h_v[k], (flags[k] & 1) != 0);
-    device_error |= r.status == LPX_DEVICE_ERROR;
+  for (int32_t k = 0; k < call.count; k++)
+    if (route[k] == LPX_ROUTE_COLD) cold.push_back(k);
+  if (cold.empty()) return 0;
+  const int32_t nc = (int32_t)cold.size();
+  std::vector<double> gb(ldb == 0 ? 0 : (size_t)nc * m), gc(ldc == 0 ? 0 : (size_t)nc * n);
+  std::vector<lpx_solve_result> res(nc);
+  std::vector<double> tx(call.x_out ? (size_t)nc * xw : 0);
+  std::vector<int32_t> tp((size_t)nc * pw, -1);   // a row the solve leaves alone (ended inside phase 1) still starts with -1
+  ScenarioCall gathered{nc, ldb == 0 ? call.b : gb.data(), ldc == 0 ? call.c : gc.data(), ldb == 0 ? 0 : m, ldc == 0 ? 0 : n,
+                        call.max_pivots, call.restore_order, call.restore_order_len, res.data(),
+                        tx.empty() ? nullptr : tx.data(), tp.empty() ? nullptr : tp.data()};
+  for (int32_t t = 0; t < nc; t++) {
+    const int32_t k = cold[t];
+    if (ldb != 0 && m > 0) memcpy(&gb[(size_t)t * m], call.b + k * ldb, (size_t)m * sizeof(double));
+    if (ldc != 0 && n > 0) memcpy(&gc[(size_t)t * n], call.c + k * ldc, (size_t)n * sizeof(double));
+    gathered.flags.push_back(call.flags[k]);
+    gathered.any_p1 |= (call.flags[k] & 2) != 0;
   }
+  if (int rc = scenarios_solve_checked(who, S, gathered)) return rc;
+  t_pivots += res[0].seconds_pivots;
+  for (int32_t t = 0; t < nc; t++) {
+    call.results[cold[t]] = res[t];
+    if (pw > 0 && tp[(size_t)t * pw] < 0) continue;
+    copy_row(xw, pw, tx.empty() ? nullptr : tx.data(), call.perm_out ? tp.data() : nullptr, t, call.x_out, call.perm_out, cold[t]);
+  }
+  return 0;
+}
+
+// the checked core of lpx_scenarios_resolve: the handle has a basis
+int scenarios_resolve_checked(const char* who, lpx_scenarios* S, const ScenarioCall& call, int32_t* route_out) {
+  const double t_start = now_s();
+  const int32_t m = S->m, n = S->n, count = call.count;
+  lpx_solve_result* results = call.results;
+  init_results(results, count);
+  lpxk::BatchResolveArgs a{};
+  a.A = S->d_A_basis.get();
+  a.perm0 = S->d_perm_basis.get();
+  a.eta = S->d_eta.get();
+  a.n_eta = S->n_eta;
+  double t_pivots = 0.0;
+  auto launch = [&] {
+    a.route = S->d_route.get();   // one of the per-scenario buffers: there for this count only now
+    return lpxk::launch_batch_resolve(a, S->stream);
+  };
+  if (int rc = launch_scenarios(S, call, a, scenario_shape(m, n, false), nullptr, launch, t_pivots)) return rc;
+  std::vector<int32_t> route(count);
+  HIP_TRY(hipMemcpyAsync(route.data(), S->d_route.get(), route.size() * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
+  if (int rc = S->scalars.fetch(S->stream)) return rc;
+  // a warm scenario's phase1_used and x0_slot are decoded like the rest: k_batch_resolve writes 0 and -1 there
+  auto warm = [&](int32_t k) { return route[k] != LPX_ROUTE_COLD; };
+  bool device_error = false;
+  for (int32_t k = 0; k < count; k++)
+    if (warm(k)) device_error |= S->scalars.decode(k, (call.flags[k] & 1) != 0, results[k]);
   if (device_error) {
     stamp_seconds(results, count, t_start, t_pivots);
     return fail(LPX_DEVICE_ERROR, std::string(who) + ": the kernel and the host disagree about a scenario's layout");
   }
-  // x and perm of the warm scenarios (their final state is always m x n): all of them, one copy each into the caller's
-  // arrays; else through a host copy, row by row -- the cold solve below reuses the device rows
-  const size_t xw = (size_t)n, pw = (size_t)n + m;
-  if (cold.empty()) {
-    if (x_out && xw > 0) HIP_TRY(hipMemcpyAsync(x_out, S->d_x, cnt * xw * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-    if (perm_out && pw > 0) HIP_TRY(hipMemcpyAsync(perm_out, S->d_perm, cnt * pw * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-    HIP_TRY(hipStreamSynchronize(S->stream));
-  } else {
-    std::vector<double> hx(x_out ? cnt * xw : 0);
-    std::vector<int32_t> hp(perm_out ? cnt * pw : 0);
-    if (!hx.empty()) HIP_TRY(hipMemcpyAsync(hx.data(), S->d_x, hx.size() * sizeof(double), hipMemcpyDeviceToHost, S->stream));
-    if (!hp.empty()) HIP_TRY(hipMemcpyAsync(hp.data(), S->d_perm, hp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, S->stream));
-    HIP_TRY(hipStreamSynchronize(S->stream));
-    for (int32_t k = 0; k < count; k++) {
-      if (h_route[k] == LPX_ROUTE_COLD) continue;
-      if (!hx.empty()) memcpy(x_out + k * xw, hx.data() + k * xw, xw * sizeof(double));
-      if (!hp.empty()) memcpy(perm_out + k * pw, hp.data() + k * pw, pw * sizeof(int32_t));
-    }
-    // the cold scenarios: lpx_scenarios_solve on their rows of b and c, gathered; results, x and perm scattered back
-    const int32_t nc = (int32_t)cold.size();
-    std::vector<double> gb(ldb == 0 ? 0 : (size_t)nc * m), gc(ldc == 0 ? 0 : (size_t)nc * n);
-    std::vector<int32_t> gflags(nc);
-    bool any_p1 = false;
-    for (int32_t t = 0; t < nc; t++) {
-      const int32_t k = cold[t];
-      if (ldb != 0 && m > 0) memcpy(&gb[(size_t)t * m], b + k * ldb, (size_t)m * sizeof(double));
-      if (ldc != 0 && n > 0) memcpy(&gc[(size_t)t * n], c + k * ldc, (size_t)n * sizeof(double));
-      gflags[t] = flags[k];
-      any_p1 |= (flags[k] & 2) != 0;
-    }
-    std::vector<lpx_solve_result> res(nc);
-    std::vector<double> tx(x_out ? (size_t)nc * xw : 0);
-    std::vector<int32_t> tp((size_t)nc * pw, -1);   // a row the solve leaves alone (ended inside phase 1) still starts with -1
-    if (int rc = scenarios_solve_checked(who, S, nc, ldb == 0 ? b : gb.data(), ldb == 0 ? 0 : m, ldc == 0 ? c : gc.data(),
-                                         ldc == 0 ? 0 : n, gflags, any_p1, max_pivots, restore_order, restore_order_len,
-                                         res.data(), tx.empty() ? nullptr : tx.data(), tp.empty() ? nullptr : tp.data()))
-      return rc;
-    t_pivots += res[0].seconds_pivots;
-    for (int32_t t = 0; t < nc; t++) {
-      const int32_t k = cold[t];
-      results[k] = res[t];
-      if (pw > 0 && tp[(size_t)t * pw] < 0) continue;
-      if (!tx.empty()) memcpy(x_out + k * xw, tx.data() + t * xw, xw * sizeof(double));
-      if (perm_out && pw > 0) memcpy(perm_out + k * pw, tp.data() + t * pw, pw * sizeof(int32_t));
-    }
-  }
-  if (route_out) memcpy(route_out, h_route.data(), cnt * sizeof(int32_t));
+  // x and perm of the warm scenarios: their final state is always m x n.  The cold solve reuses the device rows
+  if (int rc = download_rows(S, count, warm, call.x_out, call.perm_out)) return rc;
+  if (int rc = resolve_cold(who, S, call, route, t_pivots)) return rc;
+  if (route_out) memcpy(route_out, route.data(), route.size() * sizeof(int32_t));
   stamp_seconds(results, count, t_start, t_pivots);
   return 0;
+}
+
+// create, `work` on the handle, destroy: the one-shot scenario calls behind their checks.  The times are those of the
+// whole call, creation included
+template <class Work>
+int with_scenarios(int32_t m, int32_t n, const double* A, int64_t lda, const lpx_solve_options& o, const ScenarioCall& call,
+                   Work work) {
+  const double t_start = now_s();
+  DeviceRestore keep_device;
+  ScenariosGuard S;
+  if (int rc = scenarios_create_checked(m, n, A, lda, o.device, S)) return rc;
+  S->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
+  S->pricing = o.pricing;
+  if (int rc = work(S.get())) return rc;
+  stamp_seconds(call.results, call.count, t_start, call.results[0].seconds_pivots);
+  return 0;
+}
+
+// the launch-info call of a scenario kernel on this handle
+template <class Occupancy>
+int scenarios_launch_info(const char* who, lpx_scenarios* S, bool phase1, Occupancy occupancy, int32_t* threads,
+                          int32_t* lds_bytes, int32_t* blocks_per_cu) {
+  if (!S) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL handle");
+  return report_launch(S->device, scenario_shape(S->m, S->n, phase1), occupancy, threads, lds_bytes, blocks_per_cu);
 }
 
 }  // namespace
@@ -1189,12 +1226,15 @@ extern "C" int lpx_scenarios_create(int32_t m, int32_t n, const double* A, int64
   *out = nullptr;
   if (int rc = check_scenario_matrix("lpx_scenarios_create", m, n, A, lda, device)) return rc;
   DeviceRestore keep_device;
-  return scenarios_create_checked(m, n, A, lda, device, out);
+  ScenariosGuard S;
+  const int rc = scenarios_create_checked(m, n, A, lda, device, S);
+  *out = S.release();
+  return rc;
 }
 
 extern "C" void lpx_scenarios_destroy(lpx_scenarios* S) {
   DeviceRestore keep_device;
-  free_scenarios(S);
+  delete S;
 }
 
 extern "C" int lpx_scenarios_set_option(lpx_scenarios* S, int32_t key, int64_t value) {
@@ -1219,15 +1259,11 @@ extern "C" int lpx_scenarios_solve(lpx_scenarios* S, int32_t count, const double
                                    int32_t restore_order_len, lpx_solve_result* results, double* x_out, int32_t* perm_out) {
   const char* who = "lpx_scenarios_solve";
   if (!S) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL handle");
-  std::vector<int32_t> flags;
-  bool any_p1 = false;
-  if (int rc = check_scenario_solve(who, S->m, S->n, count, b, ldb, c, ldc, maximize, restore_order, restore_order_len, results,
-                                    flags, &any_p1))
-    return rc;
+  ScenarioCall call{count, b, c, ldb, ldc, max_pivots, restore_order, restore_order_len, results, x_out, perm_out};
+  if (int rc = check_scenario_solve(who, S->m, S->n, maximize, call)) return rc;
   if (count == 0) return 0;
   DeviceRestore keep_device;
-  return scenarios_solve_checked(who, S, count, b, ldb, c, ldc, flags, any_p1, max_pivots, restore_order, restore_order_len,
-                                 results, x_out, perm_out);
+  return scenarios_solve_checked(who, S, call);
 }
 
 // create, solve, destroy
@@ -1235,30 +1271,13 @@ extern "C" int lpx_solve_scenarios(int32_t m, int32_t n, const double* A, int64_
                                    int64_t ldb, const double* c, int64_t ldc, const int32_t* maximize,
                                    const lpx_solve_options* opts, lpx_solve_result* results, double* x_out, int32_t* perm_out) {
   const char* who = "lpx_solve_scenarios";
-  lpx_solve_options o{};
-  o.max_pivots = -1;
-  if (opts) o = *opts;
-  if (o.keep_state || o.perm_out || o.x_out)
-    return fail(LPX_BAD_ARGUMENT, std::string(who) + ": opts->keep_state, opts->perm_out and opts->x_out must be NULL");
-  if (o.pricing != 0 && o.pricing != 1) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": bad pricing");
+  lpx_solve_options o;
+  if (int rc = take_options(who, "opts->", false, opts, o)) return rc;
   if (int rc = check_scenario_matrix(who, m, n, A, lda, o.device)) return rc;
-  std::vector<int32_t> flags;
-  bool any_p1 = false;
-  if (int rc = check_scenario_solve(who, m, n, count, b, ldb, c, ldc, maximize, o.restore_order, o.restore_order_len, results,
-                                    flags, &any_p1))
-    return rc;
+  ScenarioCall call{count, b, c, ldb, ldc, o.max_pivots, o.restore_order, o.restore_order_len, results, x_out, perm_out};
+  if (int rc = check_scenario_solve(who, m, n, maximize, call)) return rc;
   if (count == 0) return 0;
-  const double t_start = now_s();
-  DeviceRestore keep_device;
-  ScenariosGuard guard;
-  if (int rc = scenarios_create_checked(m, n, A, lda, o.device, &guard.S)) return rc;
-  guard.S->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
-  guard.S->pricing = o.pricing;
-  if (int rc = scenarios_solve_checked(who, guard.S, count, b, ldb, c, ldc, flags, any_p1, o.max_pivots, o.restore_order,
-                                       o.restore_order_len, results, x_out, perm_out))
-    return rc;
-  stamp_seconds(results, count, t_start, results[0].seconds_pivots);   // the times of the whole call, creation included
-  return 0;
+  return with_scenarios(m, n, A, lda, o, call, [&](lpx_scenarios* S) { return scenarios_solve_checked(who, S, call); });
 }
 
 // The basis every later lpx_scenarios_resolve starts from: m variable ids (perm's numbering), NULL clears it
@@ -1280,16 +1299,12 @@ extern "C" int lpx_scenarios_resolve(lpx_scenarios* S, int32_t count, const doub
                                      int32_t* route_out) {
   const char* who = "lpx_scenarios_resolve";
   if (!S) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": NULL handle");
-  std::vector<int32_t> flags;
-  bool any_p1 = false;
-  if (int rc = check_scenario_solve(who, S->m, S->n, count, b, ldb, c, ldc, maximize, restore_order, restore_order_len, results,
-                                    flags, &any_p1))
-    return rc;
+  ScenarioCall call{count, b, c, ldb, ldc, max_pivots, restore_order, restore_order_len, results, x_out, perm_out};
+  if (int rc = check_scenario_solve(who, S->m, S->n, maximize, call)) return rc;
   if (!S->has_basis) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": the handle has no basis (lpx_scenarios_set_basis)");
   if (count == 0) return 0;
   DeviceRestore keep_device;
-  return scenarios_resolve_checked(who, S, count, b, ldb, c, ldc, flags, max_pivots, restore_order, restore_order_len, results,
-                                   x_out, perm_out, route_out);
+  return scenarios_resolve_checked(who, S, call, route_out);
 }
 
 // create, set_basis, resolve, destroy
@@ -1298,47 +1313,27 @@ extern "C" int lpx_solve_scenarios_from_basis(int32_t m, int32_t n, const double
                                               const int32_t* maximize, const lpx_solve_options* opts, lpx_solve_result* results,
                                               double* x_out, int32_t* perm_out, int32_t* route_out) {
   const char* who = "lpx_solve_scenarios_from_basis";
-  lpx_solve_options o{};
-  o.max_pivots = -1;
-  if (opts) o = *opts;
-  if (o.keep_state || o.perm_out || o.x_out)
-    return fail(LPX_BAD_ARGUMENT, std::string(who) + ": opts->keep_state, opts->perm_out and opts->x_out must be NULL");
-  if (o.pricing != 0 && o.pricing != 1) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": bad pricing");
+  lpx_solve_options o;
+  if (int rc = take_options(who, "opts->", false, opts, o)) return rc;
   if (int rc = check_scenario_matrix(who, m, n, A, lda, o.device)) return rc;
   if (!basis) return fail(LPX_BAD_ARGUMENT, std::string(who) + ": basis is NULL");
   if (int rc = check_basis(who, m, n, basis)) return rc;
-  std::vector<int32_t> flags;
-  bool any_p1 = false;
-  if (int rc = check_scenario_solve(who, m, n, count, b, ldb, c, ldc, maximize, o.restore_order, o.restore_order_len, results,
-                                    flags, &any_p1))
-    return rc;
+  ScenarioCall call{count, b, c, ldb, ldc, o.max_pivots, o.restore_order, o.restore_order_len, results, x_out, perm_out};
+  if (int rc = check_scenario_solve(who, m, n, maximize, call)) return rc;
   if (count == 0) return 0;
-  const double t_start = now_s();
-  DeviceRestore keep_device;
-  ScenariosGuard guard;
-  if (int rc = scenarios_create_checked(m, n, A, lda, o.device, &guard.S)) return rc;
-  guard.S->fused = o.fused > 0;   // 0 = the library's choice by size = two roundings here, as in lpx_solve at these sizes
-  guard.S->pricing = o.pricing;
-  if (int rc = scenarios_set_basis_checked(who, guard.S, basis, nullptr)) return rc;
-  if (int rc = scenarios_resolve_checked(who, guard.S, count, b, ldb, c, ldc, flags, o.max_pivots, o.restore_order,
-                                         o.restore_order_len, results, x_out, perm_out, route_out))
-    return rc;
-  stamp_seconds(results, count, t_start, results[0].seconds_pivots);   // the times of the whole call, creation and crash included
-  return 0;
+  return with_scenarios(m, n, A, lda, o, call, [&](lpx_scenarios* S) {   // the crash counts into the times too
+    if (int rc = scenarios_set_basis_checked(who, S, basis, nullptr)) return rc;
+    return scenarios_resolve_checked(who, S, call, route_out);
+  });
 }
 
 // What the launch of lpx_scenarios_resolve looks like for this handle, and the entries of its eta file
 // (scripts/bench_scenarios_resolve.py): not part of include/lpx.h
 extern "C" int lpxi_scenarios_resolve_launch_info(lpx_scenarios* S, int32_t* threads, int32_t* lds_bytes, int32_t* blocks_per_cu,
                                                   int32_t* etas) {
-  if (!S) return fail(LPX_BAD_ARGUMENT, "lpxi_scenarios_resolve_launch_info: NULL handle");
-  DeviceRestore keep_device;
-  HIP_TRY(hipSetDevice(S->device));
-  const int t = threads_or_env(threads_of(S->m, S->n));
-  const int lds = (int)std::min<int64_t>(std::max<int64_t>(lpxk::kBatchScratchBytes, lds_bytes_of(S->m, S->n)), INT32_MAX);
-  if (threads) *threads = t;
-  if (lds_bytes) *lds_bytes = lds;
-  if (blocks_per_cu) *blocks_per_cu = lpxk::batch_resolve_blocks_per_cu(t, lds);
+  if (int rc = scenarios_launch_info("lpxi_scenarios_resolve_launch_info", S, false, lpxk::batch_resolve_blocks_per_cu, threads,
+                                     lds_bytes, blocks_per_cu))
+    return rc;
   if (etas) *etas = S->has_basis ? S->n_eta : -1;
   return 0;
 }
@@ -1346,14 +1341,6 @@ extern "C" int lpxi_scenarios_resolve_launch_info(lpx_scenarios* S, int32_t* thr
 // What the launch of lpx_scenarios_solve looks like for this handle (scripts/bench_scenarios.py): not part of include/lpx.h
 extern "C" int lpxi_scenarios_launch_info(lpx_scenarios* S, int32_t phase1, int32_t* threads, int32_t* lds_bytes,
                                           int32_t* blocks_per_cu) {
-  if (!S) return fail(LPX_BAD_ARGUMENT, "lpxi_scenarios_launch_info: NULL handle");
-  DeviceRestore keep_device;
-  HIP_TRY(hipSetDevice(S->device));
-  const int t = threads_or_env(threads_of(S->m, S->n + (phase1 ? 1 : 0)));
-  const int lds = (int)std::min<int64_t>(std::max<int64_t>(lpxk::kBatchScratchBytes, phase1 ? solve_lds_bytes_of(S->m, S->n)
-                                                                                            : lds_bytes_of(S->m, S->n)), INT32_MAX);
-  if (threads) *threads = t;
-  if (lds_bytes) *lds_bytes = lds;
-  if (blocks_per_cu) *blocks_per_cu = lpxk::batch_scenarios_blocks_per_cu(t, lds);
-  return 0;
+  return scenarios_launch_info("lpxi_scenarios_launch_info", S, phase1 != 0, lpxk::batch_scenarios_blocks_per_cu, threads,
+                               lds_bytes, blocks_per_cu);
 }

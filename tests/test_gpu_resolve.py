@@ -57,10 +57,11 @@ def modelled(oracle, name, case, pricing="reference", budget=-1):
     return _WANT[key]
 
 
-def raw(handle, fn_name, case, budget, rows=None, shared=()):
+def raw(handle, fn_name, case, budget, rows=None, shared=(), pass_x=True, pass_perm=True):
     """lpx_scenarios_solve / lpx_scenarios_resolve through ctypes on the LPScenarios `handle` for the scenarios `rows` of
     `case` (None: all); a name in `shared` passes that vector of the first row at pitch 0.  Returns (results, x, perm,
-    route) with x and perm pre-filled with the sentinels (route: None for lpx_scenarios_solve)."""
+    route) with x and perm pre-filled with the sentinels (route: None for lpx_scenarios_solve); an array that is not
+    passed (x_out / perm_out NULL) comes back as filled."""
     from linear_programming_solver_amd import _lib
     m, n = handle.m, handle.n
     rows = list(range(len(case["maximize"]))) if rows is None else list(rows)
@@ -72,8 +73,8 @@ def raw(handle, fn_name, case, budget, rows=None, shared=()):
     x = np.full((count, n), SENTINEL_X)
     perm = np.full((count, n + m), SENTINEL_PERM, dtype=np.int32)
     args = [handle._h, count, b.ctypes.data_as(_lib.dp), m if b.ndim == 2 else 0, c.ctypes.data_as(_lib.dp),
-            n if c.ndim == 2 else 0, mx.ctypes.data_as(_lib.ip), budget, None, -1, res, x.ctypes.data_as(_lib.dp),
-            perm.ctypes.data_as(_lib.ip)]
+            n if c.ndim == 2 else 0, mx.ctypes.data_as(_lib.ip), budget, None, -1, res,
+            x.ctypes.data_as(_lib.dp) if pass_x else None, perm.ctypes.data_as(_lib.ip) if pass_perm else None]
     route = None
     if fn_name == "lpx_scenarios_resolve":
         route = np.full(count, -9, dtype=np.int32)
@@ -365,3 +366,76 @@ def test_solve_scenarios_with_a_basis(lps, oracle):
                 assert isinstance(answers[k], Exception), (name, k)
                 assert type(answers[k]) is type(expect[k]) and str(answers[k]) == str(expect[k]), (name, k)
     assert "Decimal" in kinds and len(kinds) >= 3, kinds      # optima, infeasible and unbounded scenarios
+
+
+# ------------------------------------------------------------------------------------ 5. which arrays come back
+def small_case():
+    """rc.case(5, 4) and one more scenario, 16: the b of scenario 12 (b[1] = -1e6) under the cost of scenario 5 read as a
+    `max`, which is the base's cost negated.  At the base's basis its b has a negative entry and its cost is improving:
+    cold -- the route no scenario of rc.case(5, 4) takes from that basis -- and the cold solve is infeasible, so it ends
+    inside phase 1 whatever the budget: no x, no perm."""
+    case = rc.case(5, 4)
+    case["b"] = np.vstack([case["b"], case["b"][12]])
+    case["c"] = np.vstack([case["c"], case["c"][5]])
+    case["maximize"] = case["maximize"] + [True]
+    return case
+
+
+# name: (basis (None: the base's), scenarios, their routes, which of them end inside phase 1, budget (None: above the model's))
+OUTPUT_CALLS = {
+    "cold, primal and dual": (None, [0, 12, 16, 1, 5], ["primal", "dual", "cold", "primal", "primal"], [16], None),
+    "cold, primal and dual without a pivot": (None, [0, 12, 16, 1, 5], ["primal", "dual", "cold", "primal", "primal"], [16], 0),
+    "no cold route": (None, [0, 12, 1, 5], ["primal", "dual", "primal", "primal"], [], None),
+    "every route cold": ([3, 5, 6, 7, 8], [0, 12, 3], ["cold", "cold", "cold"], [12], None),   # a basis that is not the base's
+}
+
+
+def final_n_of_the_cold_solve(oracle, case, k, budget):
+    _, st = oracle.solve(case["A"], case["b"][k], case["c"][k], case["maximize"][k], kind=oracle.FP64, max_pivots=budget,
+                         want_trace=False)
+    final_n = st.n
+    st.close()
+    return final_n
+
+
+@pytest.mark.parametrize("call", sorted(OUTPUT_CALLS))
+def test_each_choice_of_output_arrays_gets_the_same_rows(lps, oracle, call):
+    """x_out and perm_out, x_out alone, perm_out alone, neither: every array that is passed holds what the call with both
+    arrays put there, bit for bit; results (but for the times) and route_out are the same.  With and without a cold route
+    in the call, and with cold solves that end inside phase 1 (their rows keep the sentinels) beside cold solves that end
+    m x n.  The model says first that the inputs hold these routes and endings."""
+    basis, rows, routes, inside_phase1, budget = OUTPUT_CALLS[call]
+    case = small_case()
+    m, n = case["A"].shape
+    if basis is None:
+        basis = rc.base_basis(oracle, case)
+    want = rc.model_case(oracle, case, basis, -1 if budget is None else budget)
+    if budget is None:
+        budget = rc.budget_above(want)
+    assert [want[k]["route"] for k in rows] == routes, call
+    for k in rows:
+        if want[k]["route"] == "cold":
+            assert final_n_of_the_cold_solve(oracle, case, k, budget) == (n + 1 if k in inside_phase1 else n), (call, k)
+    choices = [(True, False), (False, True), (False, False)]
+    handle = lps.LPScenarios(case["A"])
+    try:
+        handle.set_basis(basis)
+        cold = raw(handle, "lpx_scenarios_solve", case, budget, rows=rows)
+        both = raw(handle, "lpx_scenarios_resolve", case, budget, rows=rows)
+        others = [raw(handle, "lpx_scenarios_resolve", case, budget, rows=rows, pass_x=px, pass_perm=pp) for px, pp in choices]
+    finally:
+        handle.close()
+    compare_all(both, cold, want, call, rows=rows)
+    for t, k in enumerate(rows):
+        if k in inside_phase1:
+            assert np.all(both[1][t] == SENTINEL_X) and np.all(both[2][t] == SENTINEL_PERM), (call, k)
+        else:
+            assert sorted(both[2][t]) == list(range(n + m)), (call, k)
+    untouched_x = np.full((len(rows), n), SENTINEL_X)
+    untouched_perm = np.full((len(rows), n + m), SENTINEL_PERM, dtype=np.int32)
+    for (px, pp), (res, x, perm, route) in zip(choices, others):
+        what = "%s: x_out %s, perm_out %s" % (call, "passed" if px else "NULL", "passed" if pp else "NULL")
+        assert [result_bytes(r) for r in res] == [result_bytes(r) for r in both[0]], what
+        assert list(route) == list(both[3]), what
+        assert x.tobytes() == (both[1] if px else untouched_x).tobytes(), what
+        assert perm.tobytes() == (both[2] if pp else untouched_perm).tobytes(), what

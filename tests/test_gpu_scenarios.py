@@ -88,9 +88,10 @@ def budget_above(want):
     return 2 * max(r["pivots1"] + r["pivots2"] for r in want) + 100
 
 
-def raw_solve(handle, L, budget, order=None):
+def raw_solve(handle, L, budget, order=None, pass_x=True, pass_perm=True):
     """lpx_scenarios_solve through ctypes on the LPScenarios `handle`; b and c of L may be 1-D (pitch 0).  Returns
-    (results, x, perm) with x and perm pre-filled with the sentinels."""
+    (results, x, perm) with x and perm pre-filled with the sentinels; an array that is not passed (x_out / perm_out
+    NULL) comes back as filled."""
     from linear_programming_solver_amd import _lib
     m, n = handle.m, handle.n
     count = len(L["maximize"])
@@ -105,8 +106,8 @@ def raw_solve(handle, L, budget, order=None):
     rc = handle._L.lpx_scenarios_solve(handle._h, count, b.ctypes.data_as(_lib.dp), m if b.ndim == 2 else 0,
                                        c.ctypes.data_as(_lib.dp), n if c.ndim == 2 else 0, mx.ctypes.data_as(_lib.ip),
                                        budget, None if keep is None else keep.ctypes.data_as(_lib.ip),
-                                       -1 if o is None else int(o.size), res, x.ctypes.data_as(_lib.dp),
-                                       perm.ctypes.data_as(_lib.ip))
+                                       -1 if o is None else int(o.size), res, x.ctypes.data_as(_lib.dp) if pass_x else None,
+                                       perm.ctypes.data_as(_lib.ip) if pass_perm else None)
     assert rc == 0, _lib.last_error()
     return res, x, perm
 
@@ -317,3 +318,38 @@ def test_solve_scenarios_matches_solve_form_by_form(lps, oracle):
                 assert np.array_equal(bits(solver.last_batch_x[k]), bits(alone.last.x)), k
                 assert list(info.perm) == list(alone.last.perm), k
     assert "Decimal" in kinds and len(kinds) >= 2, kinds      # optima, and the infeasible and unbounded scenarios' exceptions
+
+
+# ------------------------------------------------------------------------------------ 8. which arrays come back
+@pytest.mark.parametrize("budget", [1, None])
+def test_each_choice_of_output_arrays_gets_the_same_rows(lps, oracle, budget):
+    """x_out and perm_out, x_out alone, perm_out alone, neither: every array that is passed holds what the call with both
+    arrays put there, bit for bit, and the results are the same but for the times.  6 scenarios of a 4 x 4 matrix, two of
+    which need phase 1: under a budget of 1 those two end inside phase 1 (their rows keep the sentinels) and the others
+    m x n; without a budget (None: a finite one above the oracle's pivots) every scenario ends m x n."""
+    L = sc.signed_cost_launch(4, 4, count=6)
+    m, n = L["A"].shape
+    count = len(L["maximize"])
+    want = oracle_results(oracle, L, "reference", -1 if budget is None else budget, key="signed 4x4")
+    ended = [r["final_n"] for r in want]
+    if budget is None:
+        assert ended == [n] * count and any(r["phase1_used"] for r in want)
+        budget = budget_above(want)
+    else:
+        assert n + 1 in ended and n in ended
+    choices = [(True, False), (False, True), (False, False)]
+    handle = lps.LPScenarios(L["A"])
+    try:
+        both = raw_solve(handle, L, budget)
+        others = [raw_solve(handle, L, budget, pass_x=px, pass_perm=pp) for px, pp in choices]
+    finally:
+        handle.close()
+    for k, w in enumerate(want):
+        compare_scenario(both[0][k], both[1][k], both[2][k], w, "(both arrays, scenario %d)" % k)
+    untouched_x = np.full((count, n), SENTINEL_X)
+    untouched_perm = np.full((count, n + m), SENTINEL_PERM, dtype=np.int32)
+    for (px, pp), (res, x, perm) in zip(choices, others):
+        what = "x_out %s, perm_out %s" % ("passed" if px else "NULL", "passed" if pp else "NULL")
+        assert result_bytes(res) == result_bytes(both[0]), what
+        assert x.tobytes() == (both[1] if px else untouched_x).tobytes(), what
+        assert perm.tobytes() == (both[2] if pp else untouched_perm).tobytes(), what
